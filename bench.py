@@ -15,11 +15,15 @@ the N > 1 path on one GPU).
 One step = compress every block of the rank (one launch of lz4_encode_kernel) then
 decompress every compressed block (one launch of lz4_decode_kernel); inputs are generated
 on the device before timing (SURVEY App. C `gen_comp`, seed = block id).  value =
-uncompressed bytes of the job / max-over-ranks step time.  Correctness is checked after
-timing (every decoded block == its source; sampled GPU-compressed blocks restored by the
-oracle = the reference decoder restated) and the compression ratio is reported.
+uncompressed bytes of the job / max-over-ranks step time.  A plain run does only that: set
+up, warm up, time --steps steps, print the line (with the compression ratio and the
+HIP-event roofline of the timed steps themselves).  --dump-outputs DIR also writes what the
+last timed step produced (see dump_outputs) so that two builds can be compared output for
+output: the inputs depend on the arguments alone.
 
-Also in the line (rank 0, N = 1): `config2` = BASELINE config 2 (256K x 4 KiB random blocks
+With --full, correctness is checked after timing (every decoded block == its source;
+sampled GPU-compressed blocks restored by the oracle = the reference decoder restated), and
+the line also holds (rank 0, N = 1): `config2` = BASELINE config 2 (256K x 4 KiB random blocks
 compressed by the reference algorithm, decode only) with its own roofline and CPU baseline;
 `config5` = BASELINE config 5 through a real byte path: GPU encode -> frames -> loopback TCP
 connection(s) (--sock-conns, default 1) -> pinned growable rxbuf + frame
@@ -950,6 +954,53 @@ def config2_leg(args, amd, torch, stream):
     }
 
 
+DUMP_SEED = 20240607        # the block sample of --dump-outputs: fixed, so two builds agree
+DUMP_SAMPLE_BLOCKS = 64     # blocks whose bytes are written whole
+DUMP_MAX_BLOCKS = 1 << 20   # blocks with per-block figures (all of the default job)
+
+
+def dump_outputs(torch, d, rank, world, comp, csz, out, dres):
+    """--dump-outputs: what the last timed step handed its caller, as DIR/<name>.npy
+    (<name>.rank<r>.npy at N > 1), float32 / float64, under 64 MB in all at any job size:
+      block_ids       the blocks the three per-block arrays below speak of: every block of
+                      this rank, or a fixed seeded sample of 2^20 of a larger shard (f64)
+      comp_sizes      compress_batch's size of each of them (f32)
+      decode_results  decompress_batch's result of each of them (f32)
+      out_block_sums  the byte sum of each one's decoded block (f64)
+      sample_blocks   64 block ids drawn with a fixed seed (f64)
+      comp_sample     their compressed bytes, zero beyond the block's size (f32, 64 x slot)
+      out_sample      their decoded bytes (f32, 64 x block size)"""
+    os.makedirs(d, exist_ok=True)
+    nb, slot = comp.shape
+    g = torch.Generator()
+    g.manual_seed(DUMP_SEED)
+    perm = torch.randperm(nb, generator=g)
+    sample = perm[:DUMP_SAMPLE_BLOCKS].sort().values
+    ids = perm[:DUMP_MAX_BLOCKS].sort().values if nb > DUMP_MAX_BLOCKS else torch.arange(nb)
+    ids_d, sample_d = ids.cuda(), sample.cuda()
+    sums = torch.empty(len(ids), dtype=torch.int64, device="cuda")
+    for b0 in range(0, len(ids), 1 << 13):   # chunked: a gather makes a copy
+        b1 = b0 + (1 << 13)
+        blk = out[b0:b1] if len(ids) == nb else out[ids_d[b0:b1]]
+        sums[b0:b1] = blk.sum(dim=1, dtype=torch.int64)
+    cs = csz[sample_d]
+    cols = torch.arange(slot, device="cuda")
+    comp_s = comp[sample_d] * (cols[None, :] < cs[:, None])
+    arrays = {
+        "block_ids": ids.numpy().astype(np.float64),
+        "comp_sizes": csz[ids_d].cpu().numpy().astype(np.float32),
+        "decode_results": dres[ids_d].cpu().numpy().astype(np.float32),
+        "out_block_sums": sums.cpu().numpy().astype(np.float64),
+        "sample_blocks": sample.numpy().astype(np.float64),
+        "comp_sample": comp_s.cpu().numpy().astype(np.float32),
+        "out_sample": out[sample_d].cpu().numpy().astype(np.float32),
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + (".rank%d" % rank if world > 1 else "") + ".npy"), a)
+    log("[rank %d] wrote %d output arrays (%.1f MB) to %s" % (
+        rank, len(arrays), sum(a.nbytes for a in arrays.values()) / 1e6, d))
+
+
 def _free_port():
     import socket
     s = socket.socket()
@@ -1015,6 +1066,13 @@ def main():
     ap.add_argument("--kind", choices=["comp", "rand"], default="comp")
     ap.add_argument("--cpu-blocks", type=int, default=65536,
                     help="CPU-baseline sample (65536 x 64 KiB = 4 GiB)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also verify every block, time the CPU baseline "
+                         "and run the nested config-2 and config-5 legs (minutes)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step of the device-resident line produced "
+                         "as DIR/<name>.npy (sizes, results, per-block sums, a seeded sample of "
+                         "whole blocks)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-config2", action="store_true")
     ap.add_argument("--no-config5", action="store_true")
@@ -1048,6 +1106,8 @@ def main():
     ap.add_argument("--chain-cpu-bytes", type=int, default=1 << 30,
                     help="payload of the reference socket-codec baseline run")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.e2e:
         return e2e_bench(args)
     if args.sock:
@@ -1165,13 +1225,18 @@ def main():
     dec_ms = sum(e[1].elapsed_time(e[2]) for e in evs) / args.steps
     elapsed = reduce_max(dist, elapsed)
 
-    # ---- correctness + ratio (outside the timed region) ----
-    ok = bool((dres == n).all().item())
-    for b0 in range(0, nb, 1 << 14):  # chunked: a whole-tensor compare would need 64 GiB
-        ok = ok and bool(torch.equal(out[b0:b0 + (1 << 14)], src[b0:b0 + (1 << 14)]))
+    if args.dump_outputs:
+        dump_outputs(torch, args.dump_outputs, rank, world, comp, csz, out, dres)
+
+    # ---- ratio, and with --full correctness (outside the timed region) ----
+    ok = True
+    if args.full:
+        ok = bool((dres == n).all().item())
+        for b0 in range(0, nb, 1 << 14):  # chunked: a whole-tensor compare would need 64 GiB
+            ok = ok and bool(torch.equal(out[b0:b0 + (1 << 14)], src[b0:b0 + (1 << 14)]))
     comp_bytes = int(csz.to(torch.int64).sum().item())
     sample_ok = None
-    if rank == 0 and args.verify_sample > 0:
+    if rank == 0 and args.full and args.verify_sample > 0:
         try:
             orc = C.CDLL(os.path.join(ROOT, "oracle", "liblz4_oracle.so"))
             idx = torch.linspace(0, nb - 1, args.verify_sample).long()
@@ -1232,7 +1297,7 @@ def main():
                      "basis": "sum(n + c) x 2 (R+W) / step time, all ranks, vs 8 TB/s x GPUs"}}
 
     cpu = None
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         # after every rank's timed region (the gather above is a rendezvous), so at N > 1 the
         # reference's host run competes with no rank's GPU work; the other ranks only exit
         cpu = cpu_baseline(n, kind, args.cpu_blocks)
@@ -1240,7 +1305,7 @@ def main():
             cpu["note"] = ("timed by rank 0 after every rank's timed steps (the other %d "
                            "ranks are exiting)" % (world - 1))
     c2 = None
-    if rank == 0 and world == 1 and not args.no_config2:
+    if rank == 0 and world == 1 and args.full and not args.no_config2:
         del src, comp, out
         torch.cuda.empty_cache()
         c2 = config2_leg(args, amd, torch, stream)
@@ -1249,7 +1314,7 @@ def main():
                                               min_seconds=1.0, repeats=3)
 
     c5 = None
-    if rank == 0 and world == 1 and not args.no_config5:
+    if rank == 0 and world == 1 and args.full and not args.no_config5:
         try:
             torch.cuda.empty_cache()
             c5 = sock_leg(args)
@@ -1275,7 +1340,8 @@ def main():
             "hbm_read_roofline": {"bound_GiBps": round(read_bound, 1),
                                   "frac": round(value / read_bound, 4)},
             "per_gpu": per_rank,
-            "verified": bool(ok), "oracle_sample_ok": sample_ok,
+            "full": args.full, "verified": bool(ok) if args.full else None,
+            "oracle_sample_ok": sample_ok,
             "roofline": roof, "cpu_baseline": cpu, "config2": c2, "config5": c5,
         }
         print(json.dumps(line), flush=True)
