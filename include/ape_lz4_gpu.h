@@ -24,9 +24,11 @@
  * Return value of a launcher: 0 on success, otherwise a negative
  * APE_LZ4_GPU_E* code (nothing was launched); per-block status is in d_result.
  *
- * GPU limits: the encoder takes blocks of at most APE_LZ4_GPU_MAX_BLOCK (65536)
- * bytes (the LZ4 window; the benchmark's 64 KiB block); a larger input gets
- * d_result = APE_LZ4_GPU_ERANGE.  The decoder has no block-size limit.
+ * GPU limits: one encoder workgroup takes at most APE_LZ4_GPU_MAX_BLOCK (65536) bytes
+ * (the LZ4 window; the benchmark's 64 KiB block), and the compress_*_batch_dev entry
+ * points give a larger input d_result = APE_LZ4_GPU_ERANGE.  Larger inputs, up to
+ * 0x7E000000 bytes, go through APE_LZ4_compress_large_batch_dev, which compresses slices
+ * in parallel and stitches them into one block.  The decoder has no block-size limit.
  */
 #pragma once
 #include <stddef.h>
@@ -145,6 +147,51 @@ int APE_LZ4_compress_destSize_batch_scratch_dev(const char *const *d_src, int *d
                                                 char *const *d_dst, const int *d_targetDstSize,
                                                 int *d_result, int nblocks, void *d_scratch,
                                                 size_t scratch_bytes, void *stream);
+
+/* ---- inputs larger than one encoder block, as ONE LZ4 block (lz4_large.hip) ----
+ * == N x APE_LZ4_compress_fast on inputs of any size up to maxSrcSize: d_result[i] <-
+ * size of ONE valid LZ4 block of d_src[i][0, d_srcSize[i]) (decodes with decompress_safe,
+ * cap = srcSize), or 0 if it does not fit d_dstCap[i] (nothing is written then).  The
+ * output never exceeds compressBound(srcSize).
+ *
+ * maxSrcSize (1 .. 0x7E000000) is a host-side upper bound on every d_srcSize[i]: it sizes
+ * the grid and the scratch, since the sizes themselves live on the device.  A block with
+ * d_srcSize[i] > maxSrcSize gets APE_LZ4_GPU_ERANGE, a negative size 0; the other blocks of
+ * the call are unaffected.  The scratch is the caller's: 16-byte aligned device memory of
+ * at least APE_LZ4_compress_large_scratch_size(nblocks, maxSrcSize) bytes (about the batch's
+ * maxSrcSize x nblocks again), otherwise the call returns APE_LZ4_GPU_EINVAL and
+ * APE_LZ4_gpu_last_error names the size needed.  There are no internal passes: a batch that
+ * needs too much scratch is split by the caller (scratch_size returns (size_t)-1 for a batch
+ * of 2^24 or more slices, 0 for arguments out of range).  Asynchronous, no
+ * allocation, no sync, graph-capturable: four stream-ordered launches.
+ *
+ * Slicing.  An input of at most 65536 bytes is one slice and its output is byte-identical
+ * to APE_LZ4_compress_fast_batch_dev at the same acceleration.  A larger input is cut at
+ * multiples of S = APE_LZ4_compress_large_slice_size() (a compile-time constant, a multiple
+ * of 64, <= 65536 - 64); slice k is compressed with the preceding min(k*S, 65536 - len_k)
+ * bytes as history, exactly as APE_LZ4_compress_withPrefix_batch_dev does with prefix = k*S
+ * (all slices in parallel).  The block is the slices' sequences STITCHED: where slice k-1
+ * ends in a final literal run of t bytes and slice k begins with l literals, the output has
+ * one sequence of t + l literals that keeps slice k's match; a slice with no match at all
+ * only lengthens the run carried into the next slice; the block ends with one final literal
+ * run.  Every other byte is the slices' own.
+ *
+ * Decoding such a block on the GPU is still one workgroup per block (the decoder has no
+ * slice-parallel form). */
+int APE_LZ4_compress_large_slice_size(void);
+size_t APE_LZ4_compress_large_scratch_size(int nblocks, int maxSrcSize);
+int APE_LZ4_compress_large_batch_dev(const char *const *d_src, const int *d_srcSize,
+                                     char *const *d_dst, const int *d_dstCap, int *d_result,
+                                     int nblocks, int maxSrcSize, int acceleration,
+                                     void *d_scratch, size_t scratch_bytes, void *stream);
+/* Diagnostic (tools/large_bench.py): the same call with HIP events around its four launches;
+ * waits for them and returns ms4[0..4) = plan, encode, offsets, stitch in milliseconds.
+ * Synchronous, creates events: not for graph capture. */
+int APE_LZ4_compress_large_timed_dev(const char *const *d_src, const int *d_srcSize,
+                                     char *const *d_dst, const int *d_dstCap, int *d_result,
+                                     int nblocks, int maxSrcSize, int acceleration,
+                                     void *d_scratch, size_t scratch_bytes, void *stream,
+                                     float *ms4);
 
 /* One-shot routing: ape_lz4.h one-shot calls on blocks smaller than
  * `bytes` (compress: input size; decompress_safe/_partial: capacity) run the host codec,

@@ -23,6 +23,7 @@ __all__ = [
     "compress_destSize_scratch_ptr_batch", "destSize_scratch_size",
     "socket_send_blocks", "socket_recv_blocks", "socket_stats", "set_oneshot_host_below",
     "Chain",
+    "compress_large_slice_size", "compress_large_scratch_size", "compress_large_ptr_batch",
     "oneshot_on_gpu",
     "ONESHOT_HOST_ALL",
 ]
@@ -80,6 +81,9 @@ def lib():
             "APE_LZ4_decompress_safe_frames_dev": (i, [p, p, p, sz, p, p, i, p]),
             "APE_LZ4_compress_withPrefix_batch_dev": (i, [p, p, p, p, p, p, i, p]),
             "APE_LZ4_decompress_safe_usingDict_batch_dev": (i, [p, p, p, p, p, p, p, i, p]),
+            "APE_LZ4_compress_large_slice_size": (i, []),
+            "APE_LZ4_compress_large_scratch_size": (sz, [i, i]),
+            "APE_LZ4_compress_large_batch_dev": (i, [p, p, p, p, p, i, i, i, p, sz, p]),
             "APE_LZ4_rxbuf_new": (p, [sz]),
             "APE_LZ4_rxbuf_prepare": (i, [p, sz]),
             "APE_LZ4_rxbuf_append": (i, [p, p, sz]),
@@ -389,6 +393,42 @@ def compress_prefix_batch(src_ptrs, src_sizes, prefix_sizes, dst_ptrs, caps, res
     _check(lib().APE_LZ4_compress_withPrefix_batch_dev(
         _ptr(src_ptrs), _ptr(src_sizes), _ptr(prefix_sizes), _ptr(dst_ptrs), _ptr(caps),
         _ptr(results), n, _stream(stream)), "APE_LZ4_compress_withPrefix_batch_dev")
+
+
+def compress_large_slice_size():
+    """APE_LZ4_compress_large_slice_size: the slice size S of the large-input path."""
+    return lib().APE_LZ4_compress_large_slice_size()
+
+
+def compress_large_scratch_size(nblocks, max_src_size):
+    """APE_LZ4_compress_large_scratch_size: scratch bytes compress_large_ptr_batch needs."""
+    return lib().APE_LZ4_compress_large_scratch_size(nblocks, max_src_size)
+
+
+def compress_large_ptr_batch(src_ptrs, src_sizes, dst_ptrs, caps, results, max_src_size,
+                             acceleration=1, scratch=None, stream=None):
+    """N x APE_LZ4_compress_fast on inputs of any size up to max_src_size, each as ONE LZ4
+    block (slices compressed in parallel, then stitched); pointer-array form (int64 tensors of
+    pointers).  scratch: uint8 CUDA tensor of at least compress_large_scratch_size(N,
+    max_src_size) bytes, 16-byte aligned; None allocates one.  Returns the scratch."""
+    import torch
+    _arr(src_sizes, "compress_large_ptr_batch src_sizes", torch.int32)
+    n = src_sizes.shape[0]
+    _ptr_args("compress_large_ptr_batch", n, src_ptrs=(src_ptrs, _i64()), src_sizes=(src_sizes, _i32()),
+              dst_ptrs=(dst_ptrs, _i64()), caps=(caps, _i32()), results=(results, _i32()))
+    if scratch is None:
+        need = compress_large_scratch_size(n, max_src_size)
+        if need == 0 or need >= 1 << 63:
+            raise ValueError("compress_large_ptr_batch: max_src_size outside [1, 0x7E000000] "
+                             "or too many slices for one call")
+        scratch = torch.empty(need, dtype=torch.uint8, device=src_sizes.device)
+    else:
+        _arr(scratch, "compress_large_ptr_batch scratch", torch.uint8)
+    _check(lib().APE_LZ4_compress_large_batch_dev(
+        _ptr(src_ptrs), _ptr(src_sizes), _ptr(dst_ptrs), _ptr(caps), _ptr(results), n,
+        max_src_size, acceleration, _ptr(scratch), scratch.numel(), _stream(stream)),
+        "APE_LZ4_compress_large_batch_dev")
+    return scratch
 
 
 def decompress_dict_batch(src_ptrs, comp_sizes, dst_ptrs, caps, dict_ptrs, dict_sizes, results,

@@ -1302,7 +1302,7 @@ __device__ __forceinline__ void prefix_history(EncLds &S, const Blk &B, int lane
 // Table inserts (second half) never overlap the producer's lookups (first half).
 template <bool SMALL, bool ACC>
 __device__ __forceinline__ void encode_block(EncLds &S, const Blk &B, int wave, int lane,
-                                             int *result) {
+                                             int *result, int *tail) {
     STATS_DECL
     const int k0 = B.k0;
     const int nch = B.nr >= (uint32_t)kMinLength ? B.nch : k0;   // :584, shorter -> last literals only
@@ -1496,9 +1496,11 @@ __device__ __forceinline__ void encode_block(EncLds &S, const Blk &B, int wave, 
     }
     if (!E.overflow) emit_tail(S, B, lane, E);
     // ---- last literals (:732-751), from the end of the last match ----
+    uint32_t last_run = 0;
     if (!E.overflow) {
         const uint32_t anchor = E.ein;
         const uint32_t lit = B.un - anchor;
+        last_run = lit;
         const uint32_t hdr = 1u + ext_bytes(lit);
         const uint32_t total = E.o + hdr + lit;
         if (total > B.cap) {
@@ -1512,7 +1514,11 @@ __device__ __forceinline__ void encode_block(EncLds &S, const Blk &B, int wave, 
             E.o = total;
         }
     }
-    if (lane == 0) *result = E.overflow ? 0 : (int)E.o;
+    if (lane == 0) {
+        *result = E.overflow ? 0 : (int)E.o;
+        // the large-input path (lz4_large.hip) stitches slices at their final literal runs
+        if (tail) *tail = E.overflow ? 0 : (int)last_run;
+    }
     STAT_ADD(13, 1);
     STATS_FLUSH_TID(g_enc_stats, 128);
 }
@@ -1569,8 +1575,9 @@ lz4_encode_kernel(BlockArgs a) {
     for (int i = tid; i < (int)(kRingE / 16 + 4); i += 192) ((uint4 *)S.ring)[i] = make_uint4(0, 0, 0, 0);
     if (tid == 0) S.qn[0] = S.qn[1] = 0u;
     __syncthreads();
-    if (B.n < kSmall) encode_block<true, ACC>(S, B, wave, lane, &a.result[b]);
-    else encode_block<false, ACC>(S, B, wave, lane, &a.result[b]);
+    int *const tail = a.tail ? a.tail + b : nullptr;
+    if (B.n < kSmall) encode_block<true, ACC>(S, B, wave, lane, &a.result[b], tail);
+    else encode_block<false, ACC>(S, B, wave, lane, &a.result[b], tail);
 }
 
 hipError_t launch_encode(const BlockArgs &a, hipStream_t s) {

@@ -150,6 +150,8 @@ struct BlockArgs {
                               // in-chunk candidate (faster, lower ratio)
     int *result;
     int nblocks;
+    int *tail;                // encoder: per-block length of the final literal run (nullable;
+                              // the large-input path stitches slices there, lz4_large.hip)
 };
 
 hipError_t launch_decode(const BlockArgs &a, bool partial, hipStream_t s);
@@ -169,6 +171,27 @@ hipError_t launch_frame_offsets(const int *csize, long long *off, long long *scr
 int frame_scratch_elems(int n);
 hipError_t launch_frame_pack(const char *comp, size_t stride, const int *csize,
                              const long long *off, char *frames, int n, hipStream_t s);
+// Large inputs as one block (lz4_large.hip): the caller's arrays, and the scratch cut into
+// per-slot arrays (slot = input i, slice k at i * nsl + k) by large_scratch_layout.
+struct LargeArgs {
+    const char *const *src;   // caller's arrays, one entry per input
+    const int *src_size;
+    char *const *dst;
+    const int *dst_cap;
+    int *result;
+    int nblocks, max_src;
+    int nsl, nslots;          // slots per input, slots in all
+    size_t stride;            // bytes per slot buffer
+    const char **s_src;       // the encoder's arguments, one entry per slot ...
+    char **s_dst;
+    int *s_size, *s_prefix, *s_cap, *s_res, *s_tail;   // ... and its results
+    uint32_t *s_off, *s_carry, *s_lead, *s_next;       // offsets kernel -> stitch kernel
+    uint32_t *run_pos, *run_anchor;                    // per input, nsl + 1 entries
+    char *buf;                // slot buffers (the scratch base before large_scratch_layout)
+};
+int large_slice_size();
+size_t large_scratch_layout(int nblocks, int max_src, LargeArgs *out);
+hipError_t launch_large(const LargeArgs &a, int accel, hipStream_t s, hipEvent_t *ev = nullptr);
 hipError_t launch_synth(char *out, size_t stride, int n, long long first, int nblocks,
                         int kind, hipStream_t s);
 

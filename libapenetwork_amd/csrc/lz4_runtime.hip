@@ -475,6 +475,99 @@ int APE_LZ4_compress_destSize_batch_dev(const char *const *d_src, int *d_srcSize
     return finish_launch(e, "lz4_encode_kernel + lz4_destsize_kernel");
 }
 
+// ---- inputs of any size as one block (lz4_large.hip) ----
+namespace {
+constexpr int kLargeMaxSrc = 0x7E000000;   // LZ4_MAX_INPUT_SIZE (ref src/ape_lz4.h)
+}
+
+int APE_LZ4_compress_large_slice_size(void) { return large_slice_size(); }
+
+size_t APE_LZ4_compress_large_scratch_size(int nblocks, int maxSrcSize) {
+    if (nblocks < 0 || maxSrcSize < 1 || maxSrcSize > kLargeMaxSrc) return 0;
+    const size_t need = large_scratch_layout(nblocks, maxSrcSize, nullptr);
+    return need ? need : (size_t)-1;   // more slice slots than one call takes: split the batch
+}
+
+namespace {
+int large_batch(const char *const *d_src, const int *d_srcSize, char *const *d_dst,
+                const int *d_dstCap, int *d_result, int nblocks, int maxSrcSize, int acceleration,
+                void *d_scratch, size_t scratch_bytes, void *stream, hipEvent_t *ev);
+}
+
+int APE_LZ4_compress_large_batch_dev(const char *const *d_src, const int *d_srcSize,
+                                     char *const *d_dst, const int *d_dstCap, int *d_result,
+                                     int nblocks, int maxSrcSize, int acceleration,
+                                     void *d_scratch, size_t scratch_bytes, void *stream) {
+    return large_batch(d_src, d_srcSize, d_dst, d_dstCap, d_result, nblocks, maxSrcSize,
+                       acceleration, d_scratch, scratch_bytes, stream, nullptr);
+}
+
+int APE_LZ4_compress_large_timed_dev(const char *const *d_src, const int *d_srcSize,
+                                     char *const *d_dst, const int *d_dstCap, int *d_result,
+                                     int nblocks, int maxSrcSize, int acceleration,
+                                     void *d_scratch, size_t scratch_bytes, void *stream,
+                                     float *ms4) {
+    if (!ms4) return APE_LZ4_GPU_EINVAL;
+    hipEvent_t ev[5] = {};
+    hipError_t e = hipSuccess;
+    for (int q = 0; q < 5 && e == hipSuccess; q++) e = hipEventCreate(&ev[q]);
+    int rc = e == hipSuccess ? APE_LZ4_GPU_OK : finish_launch(e, "hipEventCreate");
+    if (rc == APE_LZ4_GPU_OK)
+        rc = large_batch(d_src, d_srcSize, d_dst, d_dstCap, d_result, nblocks, maxSrcSize,
+                         acceleration, d_scratch, scratch_bytes, stream, ev);
+    for (int q = 0; q < 4; q++) ms4[q] = 0.f;
+    if (rc == APE_LZ4_GPU_OK && nblocks > 0) {
+        e = hipEventSynchronize(ev[4]);
+        for (int q = 0; q < 4 && e == hipSuccess; q++) e = hipEventElapsedTime(&ms4[q], ev[q], ev[q + 1]);
+        rc = finish_launch(e, "compress_large stage events");
+    }
+    for (int q = 0; q < 5; q++)
+        if (ev[q]) (void)hipEventDestroy(ev[q]);
+    return rc;
+}
+
+namespace {
+int large_batch(const char *const *d_src, const int *d_srcSize, char *const *d_dst,
+                const int *d_dstCap, int *d_result, int nblocks, int maxSrcSize, int acceleration,
+                void *d_scratch, size_t scratch_bytes, void *stream, hipEvent_t *ev) {
+    if (nblocks < 0 || (nblocks > 0 && (!d_src || !d_srcSize || !d_dst || !d_dstCap ||
+                                         !d_result || !d_scratch))) {
+        snprintf(g_err, sizeof g_err, "invalid argument");
+        return APE_LZ4_GPU_EINVAL;
+    }
+    if (maxSrcSize < 1 || maxSrcSize > kLargeMaxSrc) {
+        snprintf(g_err, sizeof g_err, "compress_large: maxSrcSize %d outside [1, %d]", maxSrcSize,
+                 kLargeMaxSrc);
+        return APE_LZ4_GPU_EINVAL;
+    }
+    int rc = check_device();
+    if (rc) return rc;
+    if (nblocks == 0) return APE_LZ4_GPU_OK;
+    LargeArgs a{};
+    a.src = d_src;
+    a.src_size = d_srcSize;
+    a.dst = d_dst;
+    a.dst_cap = d_dstCap;
+    a.result = d_result;
+    a.nblocks = nblocks;
+    a.max_src = maxSrcSize;
+    a.buf = (char *)d_scratch;
+    const size_t need = large_scratch_layout(nblocks, maxSrcSize, &a);
+    if (need == 0) {
+        snprintf(g_err, sizeof g_err, "compress_large: %d inputs of up to %d bytes are more slices "
+                 "than one call takes; split the batch", nblocks, maxSrcSize);
+        return APE_LZ4_GPU_EINVAL;
+    }
+    if (scratch_bytes < need || ((uintptr_t)d_scratch & 15u)) {
+        snprintf(g_err, sizeof g_err, "compress_large: scratch of %zu bytes at %p, need %zu bytes "
+                 "16-byte aligned", scratch_bytes, d_scratch, need);
+        return APE_LZ4_GPU_EINVAL;
+    }
+    return finish_launch(launch_large(a, acceleration, (hipStream_t)stream, ev),
+                         "large plan + lz4_encode_kernel + offsets + stitch");
+}
+}  // namespace
+
 int APE_LZ4_compress_batch_strided_dev(const char *d_src, size_t src_stride, const int *d_srcSize,
                                        char *d_dst, size_t dst_stride, const int *d_dstCap,
                                        int *d_result, int nblocks, void *stream) {
