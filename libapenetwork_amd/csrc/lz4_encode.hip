@@ -10,32 +10,30 @@
 //
 // One 192-thread workgroup (three waves, one role each) per block; a batch holds
 // ~1M blocks, so most of the parallelism comes from many blocks in flight (9 per
-// CU).  Per block the LDS (17.5 KiB) holds a hash table like the reference's (:449-462:
-// u16 positions, a hash of 5 bytes; 7200 entries instead of 8192, see kHSize), a 1 KiB
-// ring of recent input and the hand-over records between the roles.  The input stays in
-// HBM/L2.
+// CU).  Per block the LDS (17904 bytes) holds a hash table like the reference's (:449-462:
+// u16 positions) but keyed by 7 bytes, with 7328 entries instead of 8192 and with every
+// position of the block in it (see kHSize, kKey), a 1 KiB ring of recent input and the
+// hand-over records between the roles.  The input stays in HBM/L2.
 //
 // The block is cut into chunks of 64 positions, one per lane.  The waves run in
 // lock step, two workgroup barriers per step s (each waits only on its own memory
 // operations; s_waitcnt vmcnt counts a wave's loads and stores together, in order):
-//   PRODUCER (wave 1), three chunks in flight:
-//     R(s+2)  copy chunk s+2 (loaded a step ago) into the ring;
-//     A(s+3)  load in[p, p+8) for every position p of the chunk;
-//     B(s+2)  hash in[p, p+5), read candidate T = table[h] (positions walked
-//             earlier plus match_end - 2, inserted as the reference does:
-//             :595-619, :680-706) and L = the earliest lane of the chunk with the
-//             same hash bits; load in[T-4, T+16);
-//     C1(s+1) own bytes from the ring, verify 4 bytes for T and L, measure T to 16
-//             bytes and L to 12 forward and both 4 backward, keep the longer;
+//   PRODUCER (wave 1), chunks s to s+4 in flight:
+//     R(s+2)  copy chunk s+2 (loaded two steps ago) into the ring;
+//     B(s+2)  hash in[p, p+7) for every position p of the chunk, read the candidate
+//             T = table[h], then write p into table[h] (every hashable position, right
+//             after the chunk's lookups: chunk k sees all of chunks < k); load in[T-4, T+12);
+//     A(s+4)  load in[p, p+8) for every position p of the chunk;
+//     C1(s+1) own bytes from the ring, verify 4 bytes of T, measure it to 12 bytes
+//             forward and 4 backward;
 //     S2(s+1) (second half) the truncated candidates, ranked and pushed into groups
 //             of 4 lanes, each group loading the 64 bytes that follow;
 //     C2(s)   finish the truncated lengths (+64 bytes) -> match info of chunk s.
-//   WALKER (wave 0), chunk s-1: the greedy chain on the scalar unit (a 9-instruction
+//   WALKER (wave 0), chunk s-1: the greedy chain on the scalar unit (a 12-instruction
 //     loop over the match lanes of a ballot mask, one v_readlane per member), the
-//     wave-wide extension of matches >= 80 bytes; second half: catch-up into pending
-//     literals (:623-627), table inserts of the walked positions and match_end - 2
-//     (:680, hashed from ring bytes read before the walk), never overlapping B, and the
-//     chunk's sequence records queued for the emitter.
+//     wave-wide extension of matches of 76 bytes and more; second half: catch-up into
+//     pending literals (:623-627) and the chunk's sequence records queued for the
+//     emitter.  The walker inserts nothing into the table.
 //   EMITTER (wave 2), every <= 8 steps: up to 64 queued records sized, prefix-summed
 //     and staged in LDS (token, lengths, offset, literals from the ring), then stored
 //     with one 16-byte store per lane; the last literals (:732-751) are copied with
@@ -60,106 +58,43 @@ hipError_t enc_stats_read(unsigned long long *out, int reset) {
 
 namespace {
 
+// Table entries, the hash scaled onto [0, kHSize).  7328 entries make the block's LDS 17904
+// bytes, inside the 35 x 512-byte granules that fit 9 blocks = 27 waves per CU (7 per SIMD:
+// <= 72 VGPRs); the reference's 8192 entries fit 8 blocks, +4.6 % encode time for +0.6 % ratio
+// (measured; tools/enc_model.c models the ratio per table size).
+constexpr int kHSize = 7328;
+static_assert(kHSize < 8192 && kHSize % 8 == 0, "table size");
+constexpr int kWavesPerEu = 7;       // (amdgpu_waves_per_eu: the register budget that goes with it)
+// Bytes the table hash covers (the reference: 5, :456-473).  7 keeps short chance matches from
+// pre-empting longer ones: ratio up, 23 % fewer sequences (tools/enc_model.c key study,
+// DESIGN.md 3.1).
+constexpr int kKey = 7;
+// Table inserts: the producer writes every hashable position of a chunk into the table right
+// after the chunk's lookups, so chunk k sees every position of chunks < k, and the walker
+// inserts nothing.  No in-chunk candidate beside the table's.  (The reference's insert policy,
+// an in-chunk candidate and a one-barrier step were measured, see DESIGN.md 3.1 and
+// profiles/r6_encoder_policy_ab.txt.)
 
-#ifndef APE_LZ4_HLOG
-#define APE_LZ4_HLOG 13
-#endif
-constexpr int kHLog = APE_LZ4_HLOG;
-// Table entries.  The reference's 8192 (2^13) entries make the block's LDS 20.4 KiB, so
-// 8 blocks fit a CU; 7200 entries (the hash scaled onto [0, 7200)) make it 17.5 KiB (17904 B),
-// inside the 35 x 512-byte LDS granules that fit 9 blocks = 27 waves per CU (7 per SIMD:
-// <= 72 VGPRs).  Measured on 131072 blocks: 6912 entries -4.6 % encode time vs 8192, ratio
-// 3.1464 -> 3.1279; 7200 (once the info array was single-buffered) 3.1329 at the same time
-// (tools/enc_model.c models the ratio per table size).
-// Hash key: the bytes the table hash covers (the reference: 5, :456-473).  7 by default, with
-// every position in the table (kAllPos): the longer key keeps short chance matches from
-// pre-empting longer ones -- ratio above the round-5 encoder's on App. C data and on real
-// files, 23 % fewer sequences (tools/enc_model.c key study)
-#ifndef APE_LZ4_HKEY
-#define APE_LZ4_HKEY 7
-#endif
-constexpr int kKey = APE_LZ4_HKEY;
-static_assert(kKey >= 5 && kKey <= 8, "hash key of 5..8 bytes");
-// Table inserts: 1 = the producer writes every hashable position of a chunk into the table
-// right after the chunk's lookups (no lag: chunk k sees every position of chunks < k, and the
-// walker inserts nothing); 0 = the reference's policy (:595-619, :680-706), walked positions
-// and match_end - 2, inserted by the walker a chunk behind (chunk k then sees chunks <= k - 4:
-// the repeats at 64..256 bytes that real files are full of were lost -- 6.6 % below the
-// reference's ratio on Python sources at round 5).  -8 % encode time.
-#ifndef APE_LZ4_ALLPOS
-#define APE_LZ4_ALLPOS 1
-#endif
-constexpr bool kAllPos = APE_LZ4_ALLPOS != 0;
-// One workgroup barrier per step instead of two (1).  The mid-step barrier orders the walker's
-// table inserts after the producer's lookups and the walker's read of the single info array
-// before the producer's next write; with kAllPos the walker inserts nothing, and the info array
-// can be double-buffered by chunk parity (its 512 bytes from the table), so each role runs its
-// whole step and the three meet once.  Measured: encode time unchanged (44.07 vs 44.06 ms per
-// 131072 blocks; the texture path and VALU issue, not the barriers, set the step), ratio
-// -0.24 % from the smaller table -- off
-#ifndef APE_LZ4_ONEBAR
-#define APE_LZ4_ONEBAR 0
-#endif
-constexpr bool kOneBar = APE_LZ4_ONEBAR != 0;
-static_assert(!kOneBar || kAllPos, "one barrier per step needs the producer-only table");
-constexpr uint32_t kInfoBufs = kOneBar ? 2u : 1u;
-// The in-chunk candidate L (the earliest lane of the chunk with the same 6 hash bits; an LDS
-// scratch, 4 ds_bpermute, a 12-byte measure and the pick): 1 = none.  With every position in
-// the table (kAllPos) T finds the repeats from earlier chunks at no lag, so L only adds a
-// first repeat inside one chunk: without it encode -8.7 %, decode -2.5 %, ratio -0.7 % on App.
-// C data and -1.3 % on real files (profiles/r6_encoder_policy_ab.txt).  Its scratch's 256 bytes
-// go to the table: 7328 entries.
-#ifndef APE_LZ4_NOL
-#define APE_LZ4_NOL 1
-#endif
-#ifndef APE_LZ4_TSIZE
-#if APE_LZ4_NOL && APE_LZ4_ONEBAR
-#define APE_LZ4_TSIZE 7072           // (the second info buffer takes 256 entries)
-#elif APE_LZ4_NOL
-#define APE_LZ4_TSIZE 7328
-#else
-#define APE_LZ4_TSIZE 7200
-#endif
-#endif
-constexpr int kHSize = APE_LZ4_TSIZE;
-static_assert(kHSize <= (1 << kHLog) && kHSize % 8 == 0, "table size");
-#ifndef APE_LZ4_WAVES_PER_EU
-#define APE_LZ4_WAVES_PER_EU 7
-#endif
-// T measured to 12 bytes (as L): with stage 2 finishing only the runs' last lanes, the extra
-// truncated lanes cost less than C1's fifth dword (the 16-byte C1 of rounds 2-3 measured +1.5 %;
-// same decisions -- L is taken only when T < 12 -- so the same bytes; both bases 12)
-#ifndef APE_LZ4_EAGER_T
-#define APE_LZ4_EAGER_T 12
-#endif
-constexpr uint32_t kEagerLen = APE_LZ4_EAGER_T;   // match bytes measured by C1 (T candidate)
-static_assert(kEagerLen == 8 || kEagerLen == 12 || kEagerLen == 16 || kEagerLen == 20,
-              "C1 measures T to 8, 12, 16 or 20 bytes");
-constexpr int kYW = (int)(kEagerLen + 4u) / 4;   // T-candidate dwords loaded: in[T-4, T+kEagerLen)
-constexpr uint32_t kEagerL = 12;     // ... for the in-chunk candidate L
+// Match bytes C1 measures for the table candidate T.  12: with stage 2 finishing only the runs'
+// last lanes, the extra truncated lanes cost less than a fifth dword in C1 (16 bytes measured
+// +1.5 %).
+constexpr uint32_t kEagerLen = 12;
+static_assert(kEagerLen + 4u == 16u, "in[T-4, T+kEagerLen) is one 16-byte load (loadv)");
+constexpr uint32_t kEagerL = 12;     // (remnant of the in-chunk candidate: see prod_measure)
 // Stage 2 (C2) measures only the candidates C1 left truncated (~13 % of the lanes on App.
 // C data), compacted into groups of 4 lanes that compare 16 bytes each: 64 more bytes
-// per candidate, 16 candidates per pass (a second pass is rare).
+// per candidate, 16 candidates per pass (a second pass is rare).  Of each run of truncated
+// lanes with the same offset only the last lane is measured (the others' lengths follow from
+// it, exactly: DESIGN.md 3.1).
 constexpr uint32_t kExt2 = 64;
 constexpr uint32_t kGroups = 16;
-// Stage 2 only for the last lane of each run of truncated lanes with the same offset and base
-// (the others' lengths follow from it, exactly: DESIGN.md 3.1)
-#ifndef APE_LZ4_S2RUN
-#define APE_LZ4_S2RUN 1
-#endif
-#ifndef APE_LZ4_ERING
-#define APE_LZ4_ERING 1024
-#endif
-constexpr uint32_t kRingE = APE_LZ4_ERING;  // recent input bytes (own, stage 2, end-2, literals)
-static_assert(kRingE < 65536u, "the ring holds recent input, not the block's window (DESIGN.md 3.1.1)");
-#ifndef APE_LZ4_SCRBITS
-#define APE_LZ4_SCRBITS 6
-#endif
-[[maybe_unused]] constexpr uint32_t kScr = 1u << APE_LZ4_SCRBITS;  // in-chunk candidate scratch
+constexpr uint32_t kRingE = 1024;    // recent input bytes (own, stage 2, literals)
+static_assert((kRingE & (kRingE - 1u)) == 0u && kRingE < 65536u,
+              "the ring holds recent input, not the block's window (DESIGN.md 3.1.1)");
 constexpr int kSmall = 128;          // smaller blocks take the byte-load path
 // Sequence records in flight between the walker and the emitter.  The emitter reads up to
 // 64 records into registers at a fetch (its slots are free from then on); it fetches when
-// kFetchAt are queued or every APE_EMIT_EVERY steps, and while a batch is pending it
+// kFetchAt are queued or every kEmitEvery steps, and while a batch is pending it
 // finishes that batch at once (emit_all, no fetch) when kEmitAll are queued.  The walker adds
 // at most kChunkRecs per step (a match covers >= 4 of the chunk's 64 positions).  Worst
 // case: kEmitAll - 1 queued at a pending step, + kChunkRecs before emit_all, + kChunkRecs
@@ -169,23 +104,7 @@ constexpr uint32_t kFetchAt = 48, kEmitAll = 80, kChunkRecs = 64u / 4u;
 static_assert((kQ & (kQ - 1u)) == 0u, "record ring indexed by & (kQ - 1)");
 static_assert(kEmitAll - 1u + 2u * kChunkRecs <= kQ, "walker -> emitter record ring overflow");
 static_assert(kFetchAt < kEmitAll, "a fetch precedes emit_all");
-// acceleration > 1 keeps the in-chunk candidate: the reference's table holds every earlier
-// probe with no lag, the GPU's lags a chunk or two, and at sparse probes L is what finds the
-// near matches (ratio within 1 % of the reference at a = 2, 4, 8 with it, 2.5-2.7 % below
-// without: DESIGN.md 3.1); 0 = the faster search without it
-#ifndef APE_LZ4_ACC_L
-#define APE_LZ4_ACC_L 1
-#endif
-constexpr bool kNoL = APE_LZ4_NOL != 0;
-#ifndef APE_LZ4_APF
-#define APE_LZ4_APF 1                // producer: own-bytes load A two steps ahead (else one)
-#endif
-#ifndef APE_LZ4_CAPBITS
-#define APE_LZ4_CAPBITS 1            // length caps folded into the bit-index mins (v_min3)
-#endif
-#ifndef APE_EMIT_EVERY
-#define APE_EMIT_EVERY 8             // emitter: a batch every this many steps (at most)
-#endif
+constexpr int kEmitEvery = 8;        // emitter: a batch every this many steps (at most)
 constexpr uint32_t kStage = 512;     // emitter: output bytes per batch
 constexpr uint32_t kStageAlloc = kStage + 16u + 16u + 64u;   // + alignment, slack, dummies
 
@@ -202,16 +121,12 @@ struct __attribute__((aligned(16))) EncLds {
     // 0, so that a read's dwords share one address register (ds_read2 offsets)
     uint32_t ring[kRingE / 4 + 16];
     uint16_t tab[kHSize];
-    uint2 info[kInfoBufs][64];       // producer -> walker: chunk k in [k % kInfoBufs], written in the second half of
+    uint2 info[64];                  // producer -> walker: chunk k, written in the second half of
                                      // step k, read at the start of step k + 1 (before the
                                      // producer writes chunk k + 1 after the mid barrier)
-#if !APE_LZ4_NOL
-    uint32_t scr[kScr];              // producer scratch: earliest lane per low hash bits
-#endif
     uint2 q[kQ];                     // walker -> emitter: sequence records, record r in
                                      // [r % kQ]: {lit | (match length - 4) << 16, offset}
-    uint32_t qn[2];                  // walker -> emitter: records published ([0]; kOneBar: by step
-                                     // parity, the emitter of step s reading step s - 1's)
+    uint32_t qn[2];                  // walker -> emitter: records published, in [0] ([1] stays 0)
     uint8_t __attribute__((aligned(16))) stage[kStageAlloc];   // emitter: one batch's bytes
 };
 
@@ -223,12 +138,6 @@ template <int N>
 __device__ __forceinline__ void vm_wait() {
     static_assert(N >= 0 && N < 16, "vmcnt");
     __builtin_amdgcn_s_waitcnt(N | (7 << 4) | (15 << 8));
-}
-
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 // X = L shifted by d bytes (X byte i = L byte i + d, 0 outside L), |d| < 32,
@@ -307,18 +216,14 @@ __device__ __forceinline__ void load32(gcu8 *in, int n, int pos, uint32_t (&X)[8
 // reference multiplies the 40-bit sequence by 889523592379 (:456-473), which needs
 // quarter-rate 32-bit multiplies here; any hash gives a valid stream, so this one uses
 // full-rate 24 x 24-bit multiplies (v_mul_u32_u24 / v_mad_u32_u24, which read only the low
-// 24 bits of their operands) of bytes 0-2 and 3-5 (and 6 or 6-7).  With kKey = 5 it is the
-// round-5 hash (same ratio as the reference's on App. C data, tools/enc_model.c).
+// 24 bits of their operands) of bytes 0-2, 3-5 and 6.
 __device__ __forceinline__ uint32_t hashk(uint32_t x0, uint32_t x1) {
-    uint32_t hi;
-    if constexpr (kKey == 5) hi = (x0 >> 24) | ((x1 & 0xFFu) << 8);
-    else hi = __builtin_amdgcn_alignbyte(x1, x0, 3u);   // bytes 3..6 (the multiply takes 3..5)
-    // (__umul24 returns int: do the sums and the shift unsigned)
-    uint32_t v = (uint32_t)__umul24(x0, 0x9E3779u) + (uint32_t)__umul24(hi, 0xC2B2AEu);
-    if constexpr (kKey == 7) v += (uint32_t)__umul24((x1 >> 16) & 0xFFu, 0x27D4EBu);
-    if constexpr (kKey == 8) v += (uint32_t)__umul24(x1 >> 16, 0x27D4EBu);
-    if constexpr (kHSize == (1 << kHLog)) return v >> (32 - kHLog);
-    else return __umulhi(v, (uint32_t)kHSize);   // v scaled onto [0, kHSize): one v_mul_hi_u32
+    static_assert(kKey == 7, "hashk covers bytes 0..6");
+    const uint32_t hi = __builtin_amdgcn_alignbyte(x1, x0, 3u);   // bytes 3..6 (the multiply takes 3..5)
+    // (__umul24 returns int: do the sums unsigned)
+    const uint32_t v = (uint32_t)__umul24(x0, 0x9E3779u) + (uint32_t)__umul24(hi, 0xC2B2AEu) +
+                       (uint32_t)__umul24((x1 >> 16) & 0xFFu, 0x27D4EBu);
+    return __umulhi(v, (uint32_t)kHSize);   // v scaled onto [0, kHSize): one v_mul_hi_u32
 }
 
 // v_ffbl_b32 / v_ffbh_u32: lowest / highest set bit, 0xFFFFFFFF for 0 (inline asm
@@ -334,26 +239,23 @@ __device__ __forceinline__ uint32_t ffbh(uint32_t d) {
     return r;
 }
 
-// first differing bit of dwords A[K0..K1) vs B (bit index from A[K0]'s bit 0), or
+// first differing bit of dwords A[K0..4) vs B (bit index from A[K0]'s bit 0), or
 // 0xFFFFFFFF: ffbl + saturating add + min3 per dword, no compares or selects
-template <int K0, int K1, int NA, int NB>
+template <int K0, int NA, int NB>
 __device__ __forceinline__ uint32_t first_diff_bit(const uint32_t (&A)[NA], const uint32_t (&B)[NB]) {
-    static_assert(K1 <= NA && K1 <= NB, "dwords");
+    static_assert(NA >= 4 && NB >= 4, "dwords");
     uint32_t m = ffbl(A[K0] ^ B[K0]);
 #pragma unroll
-    for (int k = K0 + 1; k < K1; k++)
+    for (int k = K0 + 1; k < 4; k++)
         m = umin(m, __builtin_elementwise_add_sat(ffbl(A[k] ^ B[k]), 32u * (uint32_t)(k - K0)));
     return m;
 }
 
-// common length of X and Y from byte 4 (dword 1) on, up to kEagerLen.  The cap is applied to
-// the bit index (one v_min3 with the dwords' own min) instead of to the byte count afterwards
+// common length of the match at p (X = in[p-4, p+12), ...) and its candidate (Y likewise), whose
+// first 4 bytes (dword 1) are known equal, up to kEagerLen.  The cap is applied to the bit
+// index (one v_min3 with the dwords' own min) instead of to the byte count afterwards
 __device__ __forceinline__ uint32_t eager(const uint32_t (&X)[6], const uint32_t (&Y)[6]) {
-#if APE_LZ4_CAPBITS
-    return (umin(first_diff_bit<2, kYW>(X, Y), 8u * (kEagerLen - 4u)) >> 3) + 4u;
-#else
-    return umin((first_diff_bit<2, kYW>(X, Y) >> 3) + 4u, kEagerLen);
-#endif
+    return (umin(first_diff_bit<2>(X, Y), 8u * (kEagerLen - 4u)) >> 3) + 4u;
 }
 
 // bytes equal just before the match (in[p-1] == in[c-1], ...), 0..4
@@ -390,9 +292,9 @@ __device__ __forceinline__ void put_len(gu8 *o, uint32_t v) {
     o[k] = (uint8_t)v;
 }
 
-// 16 / 8 input bytes at x from the ring (the mirrored tail keeps a read that starts in
+// 16 input bytes at x from the ring (the mirrored tail keeps a read that starts in
 // the last 64 bytes contiguous): aligned dword reads + v_alignbyte.  (Measured against
-// single unaligned ds_read_b128 / _b64 (round 4): 12.5 vs 11.3 ms per 16384
+// a single unaligned ds_read_b128 (round 4): 12.5 vs 11.3 ms per 16384
 // blocks -- fewer VALU instructions, but a 1-byte lane stride makes the unaligned reads
 // slow.)
 __device__ __forceinline__ uint4 ring16(const EncLds &S, uint32_t x) {
@@ -402,40 +304,23 @@ __device__ __forceinline__ uint4 ring16(const EncLds &S, uint32_t x) {
     return make_uint4(__builtin_amdgcn_alignbyte(w1, w0, sh), __builtin_amdgcn_alignbyte(w2, w1, sh),
                       __builtin_amdgcn_alignbyte(w3, w2, sh), __builtin_amdgcn_alignbyte(w4, w3, sh));
 }
-__device__ __forceinline__ uint2 ring8(const EncLds &S, uint32_t x) {
-    const uint32_t *r = S.ring + ((x >> 2) & (kRingE / 4 - 1));
-    const uint32_t sh = x & 3u;
-    const uint32_t w0 = r[0], w1 = r[1], w2 = r[2];
-    return make_uint2(__builtin_amdgcn_alignbyte(w1, w0, sh), __builtin_amdgcn_alignbyte(w2, w1, sh));
-}
 
-// NW dwords in[pos, pos + 4 NW) (NW = 4 or 6).  fast: the window lies inside [0, n)
-// (vector loads); otherwise byte loads, bytes outside [0, n) read as 0 (the edge steps
-// and blocks below kSmall only).
-template <int NW, int NA>
+// 4 dwords in[pos, pos + 16).  fast: the window lies inside [0, n) (one vector load);
+// otherwise byte loads, bytes outside [0, n) read as 0 (the edge steps and blocks below
+// kSmall only).
+template <int NA>
 __device__ __forceinline__ void loadv(gcu8 *in, uint32_t un, uint32_t pos, uint32_t (&X)[NA],
                                       bool fast) {
-    static_assert(NW >= 3 && NW <= 6 && NW <= NA, "loadv");
+    static_assert(NA >= 4, "loadv");
     if (fast) {
-        if constexpr (NW == 3) {
-            const uint3 a = gload12(in + pos);
-            X[0] = a.x; X[1] = a.y; X[2] = a.z;
-            return;
-        }
         const uint4 a = gload16(in + pos);
         X[0] = a.x; X[1] = a.y; X[2] = a.z; X[3] = a.w;
-        if constexpr (NW == 6) {
-            const uint2 b = gload8(in + pos + 16u);
-            X[4] = b.x; X[5] = b.y;
-        } else if constexpr (NW == 5) {
-            X[4] = gload4(in + pos + 16u);
-        }
         return;
     }
 #pragma unroll
-    for (int k = 0; k < NW; k++) X[k] = 0;
+    for (int k = 0; k < 4; k++) X[k] = 0;
 #pragma unroll
-    for (uint32_t t = 0; t < 4u * NW; t++)
+    for (uint32_t t = 0; t < 16u; t++)
         if (pos + t < un) X[t >> 2] |= (uint32_t)in[pos + t] << (8 * (t & 3));
 }
 
@@ -469,13 +354,12 @@ struct Blk {
     int k0;                          // first chunk to encode: positions [0, 64 k0) are the
                                      // history prefix (withPrefix encode), only hashed
     uint32_t nr;                     // bytes to encode (n - 64 k0)
-    bool noL;                        // acceleration > 1: no in-chunk candidate
     uint32_t stride;                 // acceleration (compress_fast): the first search step
 };
 
 // ---------------- producer ----------------
 struct Part {                        // C1 result of one chunk, finished by C2
-    uint32_t len, c, bk, lim, base;      // base: bytes C1 measured (kEagerLen / kEagerL)
+    uint32_t len, c, bk, lim, base;  // base: bytes C1 measured (kEagerLen)
     uint32_t iy;                     // info.y: offset (0 = no candidate) | h << 16, formed in C1
                                      // while `has` is a lane mask (a bool carried to C2 was
                                      // materialised as 0/1 and compared again)
@@ -491,7 +375,7 @@ struct Part {                        // C1 result of one chunk, finished by C2
 // C1 for C2.
 struct PSet {
     uint32_t X[2];                   // own bytes in[p, p+8) of the chunk B works on next
-    uint32_t Y[6];                   // T-candidate bytes in[T-4, T+kEagerLen)
+    uint32_t Y[6];                   // T-candidate bytes in[T-4, T+kEagerLen) (4 dwords used)
     uint32_t E[4];                   // stage-2 candidate bytes of this lane's group
     uint32_t cT, jL, h;
     Part q;
@@ -522,14 +406,14 @@ __device__ __forceinline__ void prod_fetch_t(const Blk &B, int k, int lane, uint
     const uint32_t p = 64u * (uint32_t)k + (uint32_t)lane;
     if (FAST) {   // any address in [0, p): a lane whose T is not a candidate (C1 rechecks
                   // cT < p and cT >= 4) loads harmless bytes -- min + saturating subtract
-        loadv<kYW>(B.in, B.un, __builtin_elementwise_sub_sat(umin(cT, p - 1u), 4u), Y, true);
+        loadv(B.in, B.un, __builtin_elementwise_sub_sat(umin(cT, p - 1u), 4u), Y, true);
         return;
     }
     const bool tryT = k < B.nch && cT < p && cT >= 4u;
-    loadv<kYW>(B.in, B.un, tryT ? cT - 4u : 0u, Y, !SMALL && 64 * k + 83 <= B.n);
+    loadv(B.in, B.un, tryT ? cT - 4u : 0u, Y, !SMALL && 64 * k + 83 <= B.n);
 }
 
-// B(k): hash, table + in-chunk candidates, T fetch issue
+// B(k): hash, table candidate T, table insert, T fetch issue
 template <bool SMALL, bool FAST = false>
 __device__ __forceinline__ void prod_lookup(EncLds &S, const Blk &B, int k, int lane,
                                             const uint32_t (&X)[2], uint32_t &cT, uint32_t &jL,
@@ -539,26 +423,14 @@ __device__ __forceinline__ void prod_lookup(EncLds &S, const Blk &B, int k, int 
     const bool hashable = FAST || (k < B.nch && p + 5u <= B.un);
     h = hashk(X[0], X[1]);
     cT = S.tab[h];
-    jL = 0xFFFFFFFFu;
-    if (!kNoL && !B.noL) {   // wave-uniform
-#if !APE_LZ4_NOL
-        const uint32_t hs = h & (kScr - 1u);
-        if (hashable) atomicMin(&S.scr[hs], (uint32_t)lane);
-        wave_sync();
-        jL = hashable ? S.scr[hs] : 0xFFFFFFFFu;
-        wave_sync();
-        if (hashable) S.scr[hs] = 0xFFFFFFFFu;
-#endif
-    }
-    if constexpr (kAllPos) {
-        // after this chunk's lookups (one wave's LDS operations complete in order); lanes with
-        // the same slot: the last lane's write lands last, the latest position wins
-        if (hashable) S.tab[h] = (uint16_t)p;
-    }
+    jL = 0xFFFFFFFFu;   // (remnant of the in-chunk candidate: see prod_measure)
+    // after this chunk's lookups (one wave's LDS operations complete in order); lanes with
+    // the same slot: the last lane's write lands last, the latest position wins
+    if (hashable) S.tab[h] = (uint16_t)p;
     prod_fetch_t<SMALL, FAST>(B, k, lane, cT, Y);
 }
 
-// R(k): ring copy of chunk k (own bytes for C1 and stage 2, match_end - 2, literals; zero
+// R(k): ring copy of chunk k (own bytes for C1 and stage 2, literals; zero
 // past the block end), at the start of step k - 2, right before C1(k - 1) reads chunks k - 1
 // and k from the ring (same wave: in order)
 template <bool FAST = false>
@@ -572,7 +444,8 @@ __device__ __forceinline__ void prod_ring(EncLds &S, const Blk &B, int k, int la
     }
 }
 
-// own bytes in[p-4, p+20) of chunk k from the ring (ring tail = 0 before 0)
+// own bytes in[p-4, p+20) of chunk k from the ring (ring tail = 0 before 0; C1 uses the
+// first 16, the compiler drops the rest)
 __device__ __forceinline__ void prod_own(const EncLds &S, int k, int lane, uint32_t (&X)[6]) {
     const uint32_t p = 64u * (uint32_t)k + (uint32_t)lane;
     // 7 aligned dwords, 6 alignbytes
@@ -607,27 +480,15 @@ __device__ __forceinline__ uint32_t stage2_len(const EncLds &S, int lane, uint32
     const uint4 o = ring16(S, eo);
     const uint32_t O[4] = {o.x, o.y, o.z, o.w};
     const uint32_t li = 128u * ((uint32_t)lane & 3u);
-#if APE_LZ4_CAPBITS   // the cap 8 kExt2 bits joins the lane's own min (no min after the quad's)
-    uint32_t d = umin(first_diff_bit<0, 4>(O, E), 8u * kExt2 - li) + li;   // (no overflow)
-#else
-    uint32_t d = __builtin_elementwise_add_sat(first_diff_bit<0, 4>(O, E), li);
-#endif
+    uint32_t d = umin(first_diff_bit<0>(O, E), 8u * kExt2 - li) + li;   // (no overflow)
     d = umin(d, dpp<0xB1>(0u, d));   // quad_perm [1,0,3,2]
     d = umin(d, dpp<0x4E>(0u, d));   // quad_perm [2,3,0,1]
-#if APE_LZ4_CAPBITS
     const uint32_t len = d >> 3;     // <= kExt2
-#else
-    const uint32_t len = umin(d >> 3, kExt2);
-#endif
-#if APE_LZ4_S2RUN   // continuation point + length: a run member subtracts its own
     return eo + len;
-#else
-    return len;
-#endif
 }
 
-// C1(k): verify / measure to kEagerLen bytes / pick; queue the truncated candidates and issue
-// the stage-2 loads of the first kGroups of them
+// C1(k): verify the T candidate and measure it to kEagerLen bytes; mark the truncated lanes
+// and, of them, the ones stage 2 measures
 template <bool SMALL, bool FAST = false>
 __device__ __forceinline__ void prod_measure(EncLds &S, const Blk &B, int k, int lane,
                                              const uint32_t (&X)[6], const uint32_t (&Y)[6],
@@ -638,33 +499,26 @@ __device__ __forceinline__ void prod_measure(EncLds &S, const Blk &B, int k, int
     const bool live = FAST || k < B.nch;
     R.hashable = FAST || (live && p + 5u <= B.un);
     const bool can = FAST || (live && p >= 1u && p <= B.mstart && B.n >= kMinLength);
+    // Remnant of the in-chunk candidate L (measured): nothing fills jL any
+    // more, so okL is false and the compiler drops every line that names cL, Z, eL, lL, pickL
+    // or base.  Deleting those lines reorders instructions inside the step loops
+    // (profiles/encoder_strip_asm_diff.txt), so they leave in a change that is measured.
     const uint32_t cL = 64u * (uint32_t)k + jL;
-    // L candidate bytes in[cL-4, cL+12) from lane jL's own bytes (4 ds_bpermute; reading
-    // them from the ring beside X, in the same LDS round trip, measured +2.3 % encode time:
-    // 5 ds_read + 4 v_alignbyte)
     uint32_t Z[4];
 #pragma unroll
     for (int t = 0; t < 4; t++) Z[t] = bperm(X[t], jL);
+    constexpr bool okL = false;
     // (bitwise on bools: lane masks combined by the scalar unit, no materialised 0/1)
     const bool okT = can & (cT < p) & (cT >= 4u) & (Y[1] == X[1]);
-    // (no cL != cT test: when L's candidate is T's, L is kept only when T < 12 bytes, and then
-    // both give the same position, length and preceding bytes)
-    const bool okL = !kNoL && (can & (jL < (uint32_t)lane) & (Z[1] == X[1]));   // jL = ~0 if noL
     // (FAST: the match limit lies >= 132 bytes past every lane, beyond anything C1 and C2
     // measure, so it never cuts a length: no limit arithmetic at all)
     R.lim = FAST ? 0xFFFFu : (can ? B.mlimit - p : 0u);   // (a FAST chunk finished by a
                                                             // general step: no cut either)
-    // measured unconditionally (selects, no branches): every lane reads Y, so the
-    // compiler sees the candidate load consumed on every path.  T to 16 bytes, L to 12:
-    // L (the closer one) is taken when T is shorter than 12 and L at least as long,
-    // and C2 continues the taken candidate from where C1 stopped
-    // (tools/enc_model.c model4, pol 7 vs 0: ratio -0.1 %; measured -0.06 %, -3.4 % VALU).
+    // measured unconditionally (a select, no branch): every lane reads Y, so the
+    // compiler sees the candidate load consumed on every path; C2 continues from where
+    // C1 stopped
     const uint32_t eT = eager(X, Y);
-#if APE_LZ4_CAPBITS
-    const uint32_t eL = (umin(first_diff_bit<2, 4>(X, Z), 8u * (kEagerL - 4u)) >> 3) + 4u;
-#else
-    const uint32_t eL = umin((first_diff_bit<2, 4>(X, Z) >> 3) + 4u, kEagerL);
-#endif
+    const uint32_t eL = (umin(first_diff_bit<2>(X, Z), 8u * (kEagerL - 4u)) >> 3) + 4u;
     const uint32_t lT = okT ? eT : 0u, lL = okL ? eL : 0u;
     const bool pickL = okL & (!okT | ((lT < kEagerL) & (lL >= lT)));
     R.c = pickL ? cL : cT;
@@ -678,7 +532,6 @@ __device__ __forceinline__ void prod_measure(EncLds &S, const Blk &B, int k, int
         R.tmask = wave_ballot(R.len >= R.base) & wave_ballot(R.lim > R.base);
         R.len = umin(R.len, R.lim);
     }
-#if APE_LZ4_S2RUN
     {   // lane i + 1 truncated with the same offset and base: in[p, p+1) == in[c, c+1), so the
         // match from p is one byte longer than lane i + 1's (and lim one larger): only the
         // run's last lane is measured
@@ -686,9 +539,6 @@ __device__ __forceinline__ void prod_measure(EncLds &S, const Blk &B, int k, int
         const uint32_t keyn = dpp_z<kDppWaveShl1>(key);   // lane 63: 0, never a key
         R.smask = R.tmask & ~((R.tmask >> 1) & wave_ballot(key == keyn));
     }
-#else
-    R.smask = R.tmask;
-#endif
     R.bk = umin(back4(X[0], pickL ? Z[0] : Y[0]), R.c);  // c - back >= 0
     R.iy = ((okT | okL) ? p - R.c : 0u) | (h << 16);
 }
@@ -705,7 +555,7 @@ __device__ __forceinline__ void prod_stage2_issue(const EncLds &S, const Blk &B,
     uint32_t cb;
     const bool ga = stage2_group(R, lane, 0u, p, cb, R.eo);
     // cb + 16 <= c + base + kExt2 < p + 80 (c < p)
-    loadv<4>(B.in, B.un, ga ? cb : 0u, E, FAST || (!SMALL && 64 * k + 148 <= B.n));
+    loadv(B.in, B.un, ga ? cb : 0u, E, FAST || (!SMALL && 64 * k + 148 <= B.n));
 }
 
 // C2(k): finish the truncated lengths against the ring -> info
@@ -720,26 +570,22 @@ __device__ __forceinline__ void prod_finish(EncLds &S, const Blk &B, int k, int 
         for (uint32_t first = kGroups; first < R.ntr; first += kGroups) {   // rare
             uint32_t cb, eo, E2[4];
             const bool ga = stage2_group(R, lane, first, p, cb, eo);
-            loadv<4>(B.in, B.un, ga ? cb : 0u, E2, FAST || (!SMALL && 64 * k + 148 <= B.n));
+            loadv(B.in, B.un, ga ? cb : 0u, E2, FAST || (!SMALL && 64 * k + 148 <= B.n));
             const uint32_t m2 = bperm(stage2_len(S, lane, eo, E2), 4u * (R.rank - first));
             if (R.rank - first < kGroups) mine = m2;
         }
         if (lane_in(R.tmask)) {
-#if APE_LZ4_S2RUN   // mine - p = the run's last lane's length + the distance to it
+            // mine - p = the run's last lane's length + the distance to it
             const uint32_t cap = R.base + kExt2, full = mine - p;
             len = FAST ? umin(full, cap) : umin(umin(full, cap), R.lim);
             trunc = full >= cap && (FAST || R.lim > cap);
-#else
-            len = FAST ? R.base + mine : umin(R.base + mine, R.lim);
-            trunc = mine == kExt2 && (FAST || R.lim > R.base + kExt2);
-#endif
         }
     }
     // (FAST: the chunk lies inside the block, every lane hashable -- also the prologue's
     // chunk when the first step is FAST)
-    S.info[(uint32_t)k & (kInfoBufs - 1u)][lane] = make_uint2(len | (R.bk << 8) | (trunc ? I_TRUNC : 0u) |
+    S.info[lane] = make_uint2(len | (R.bk << 8) | (trunc ? I_TRUNC : 0u) |
                                   ((FAST || R.hashable) ? I_HASHABLE : 0u),
-                                     R.iy);
+                              R.iy);
 }
 
 // ---------------- walker ----------------
@@ -821,69 +667,39 @@ __device__ __forceinline__ uint32_t extend_match(const Blk &B, uint32_t m, uint3
     return L > lm ? lm : L;
 }
 
-// Walk chunk k (first half of step k + 1), then (second half) insert the walked
-// positions and match_end - 2 into the table and hand the members to the emitter.
+// Walk chunk k (first half of step k + 1), then (second half) hand the members to the
+// emitter; the walker inserts nothing into the table.
 // The greedy chain (:591-627: a position with a match jumps past it, any other
 // position is a literal): the scalar unit hops over the match lanes only (ballot
-// mask, one v_readlane per member); walked positions, catch-up limits (:623-627)
-// and the new anchor follow for all 64 lanes at once from the member set.  A match
-// the producer could not finish (TRUNC, >= 60 bytes) is extended by the whole wave.
+// mask, one v_readlane per member); the catch-up limits (:623-627) and the new anchor
+// follow from the member set.  A match the producer could not finish (TRUNC,
+// kEagerLen + kExt2 = 76 bytes) is extended by the whole wave.
 struct WalkOut {
-    uint64_t walked, members;
+    uint64_t members;
     uint32_t m_back, m_len, an;   // per member lane
     uint2 iv;
     uint32_t q0, Lf;              // walk start; forward match length per lane
-    uint2 e2v;                    // in[e2, e2 + 8), e2 = match_end - 2 (read before the walk)
-    uint32_t e2h;                 // its hash
-    uint32_t pmv, pe;             // kWalkPm: per member lane, the end of the match before it
-                                  // (relative to the chunk start); the last match end (relative)
+    uint2 e2v;                    // (e2v, e2h: unused, as q0 is.  Remnants of the walker's table
+    uint32_t e2h;                 // inserts: without them the step loops' registers are renumbered,
+                                  // profiles/encoder_strip_asm_diff.txt)
+    uint32_t pmv, pe;             // without acceleration: per member lane, the end of the match
+                                  // before it (relative to the chunk start), written by the hop
+                                  // chain; the last match end (relative)
 };
 
-// The walker's catch-up limits from the hop chain itself (1): the chain writes each member's
-// previous match end into its lane (v_writelane) as it finds it, instead of a wave-wide max
-// scan over the member ends afterwards (with kAllPos and no acceleration only: the walked set,
-// which needs the limit on every lane, is not used then).  Same bytes, -0.4..-0.5 % encode
-// time (profiles/r6_encoder_policy_ab.txt call 21)
-#ifndef APE_LZ4_WPM
-#define APE_LZ4_WPM 1
-#endif
-constexpr bool kWalkPm = APE_LZ4_WPM != 0 && kAllPos;
-
-// The walker's hop chain from walk position rel (< 64): shift, find-first, add, mark,
-// v_readlane, compare, branch -- 9 scalar-unit instructions per member (the compiler's loop
-// took 13).  nxt (per lane) = the walk position after the lane's match; leaves with rel >= 64
-// (64: no match lane left), j = the last member, its bit set in M.
-[[maybe_unused]] __device__ __forceinline__ void hop_chain(uint64_t Hm, uint32_t nxt, uint32_t &rel, uint64_t &M,
-                                          uint32_t &j) {
-    uint64_t t;
-    asm volatile(
-        "1:\n\t"
-        "s_lshr_b64 %[t], %[hm], %[rel]\n\t"
-        "s_cmp_eq_u64 %[t], 0\n\t"
-        "s_cbranch_scc1 2f\n\t"
-        "s_ff1_i32_b64 %[j], %[t]\n\t"
-        "s_add_u32 %[j], %[j], %[rel]\n\t"
-        "s_bitset1_b64 %[m], %[j]\n\t"
-        "v_readlane_b32 %[rel], %[nxt], %[j]\n\t"
-        "s_cmp_lt_u32 %[rel], 64\n\t"
-        "s_cbranch_scc1 1b\n\t"
-        "s_branch 3f\n"
-        "2:\n\t"
-        "s_mov_b32 %[rel], 64\n"
-        "3:"
-        : [rel] "+s"(rel), [m] "+s"(M), [j] "+s"(j), [t] "=&s"(t)
-        : [hm] "s"(Hm), [nxt] "v"(nxt)
-        : "scc");
-}
-// ... also writing pe (the previous match end) into lane j of pmv for each member j, pe then
-// the member's end (12 instructions per member).  The lane select goes through m0 (a VALU
+// The walker's hop chain from walk position rel (< 64): shift, find-first, add, mark, write
+// pe (the previous match end) into lane j of pmv, v_readlane, pe = the member's end, compare,
+// branch -- 12 scalar-unit instructions per member.  nxt (per lane) = the walk position after
+// the lane's match; leaves with rel >= 64 (64: no match lane left), j = the last member, its bit
+// set in M.  Writing each member's previous match end as the chain finds it replaces a
+// wave-wide max scan over the member ends afterwards: same bytes, -0.4..-0.5 % encode time
+// (profiles/r6_encoder_policy_ab.txt call 21).  The lane select goes through m0 (a VALU
 // instruction reads one SGPR on gfx9); nothing else in this kernel uses m0 (LDS instructions
 // do not on gfx950; tests/test_product_abi.py::test_encoder_m0_only_in_hop_chain checks the ISA)
-
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Winline-asm"   // (m0 declared clobbered: see above)
-__device__ __forceinline__ void hop_chain_pm(uint64_t Hm, uint32_t nxt, uint32_t &rel, uint64_t &M,
-                                             uint32_t &j, uint32_t &pe, uint32_t &pmv) {
+__device__ __forceinline__ void hop_chain(uint64_t Hm, uint32_t nxt, uint32_t &rel, uint64_t &M, uint32_t &j,
+                                          uint32_t &pe, uint32_t &pmv) {
     uint64_t t;
     asm volatile(
         "1:\n\t"
@@ -909,23 +725,18 @@ __device__ __forceinline__ void hop_chain_pm(uint64_t Hm, uint32_t nxt, uint32_t
 }
 #pragma clang diagnostic pop
 
-// First half: the hop chain only (the latency-bound part); second half, before the
-// inserts: the lane-parallel catch-up limits, walked set and anchor (walk_finish).
+// First half: the hop chain only (the latency-bound part); second half: the lane-parallel
+// catch-up limits and the anchor (walk_finish).
 template <bool ACC>
 __device__ __forceinline__ void walk_chain(const EncLds &S, const Blk &B, int k, int lane, Walk &W,
                                            WalkOut &O) {
     const uint32_t P = 64u * (uint32_t)k;
-    O.walked = O.members = 0;
+    O.members = 0;
     O.m_back = O.m_len = O.an = 0;
-    O.iv = S.info[(uint32_t)k & (kInfoBufs - 1u)][lane];
+    O.iv = S.info[lane];
     O.q0 = W.q;
-    O.pe = W.anchor - P;                                 // (kWalkPm; u32 wrap below P)
+    O.pe = W.anchor - P;                                 // (u32 wrap below P)
     O.Lf = O.iv.x & 0x7Fu;                               // forward match length
-    // match_end - 2 (:680) of every lane's match, read from the ring now so that the
-    // second half's hash needs no LDS round trip (the ring holds chunks k - 13 .. k + 2,
-    // and a match the producer finished ends before p + 81; a match the walker extends
-    // is hashed from the input instead)
-    if constexpr (!kAllPos) O.e2v = ring8(S, P + (uint32_t)lane + O.Lf - 2u);
     if (W.q >= P + 64u) return;               // a match from earlier chunks covers it
     const uint2 iv = O.iv;
     const uint64_t Hm = wave_ballot(O.Lf != 0u);          // lanes with a match
@@ -937,8 +748,7 @@ __device__ __forceinline__ void walk_chain(const EncLds &S, const Blk &B, int k,
         // lane's match, +256 marking a match the producer could not finish.
         const uint32_t nxt = (uint32_t)lane + (iv.x & 0x7Fu) + ((iv.x & 0x80u) << 1);
         uint32_t j = 0;
-        if constexpr (kWalkPm) hop_chain_pm(Hm, nxt, rel, M, j, O.pe, O.pmv);
-        else hop_chain(Hm, nxt, rel, M, j);
+        hop_chain(Hm, nxt, rel, M, j, O.pe, O.pmv);
         while (__builtin_expect(rel >= 256u, 0)) {   // unfinished (rare): the wave extends it
             const uint32_t me = P + j;
             const uint32_t cm = me - (lane_val(iv.y, (int)j) & 0xFFFFu);
@@ -947,8 +757,7 @@ __device__ __forceinline__ void walk_chain(const EncLds &S, const Blk &B, int k,
             rel = j + Le;
             O.pe = rel;
             if (rel >= 64u) break;
-            if constexpr (kWalkPm) hop_chain_pm(Hm, nxt, rel, M, j, O.pe, O.pmv);
-            else hop_chain(Hm, nxt, rel, M, j);
+            hop_chain(Hm, nxt, rel, M, j, O.pe, O.pmv);
         }
         O.members = M;
         W.q = P + rel;
@@ -990,17 +799,13 @@ __device__ __forceinline__ void walk_chain(const EncLds &S, const Blk &B, int k,
 template <bool ACC>
 __device__ __forceinline__ void walk_finish(const Blk &B, int k, int lane, Walk &W, WalkOut &O) {
     const uint32_t P = 64u * (uint32_t)k;
-    // match_end - 2's hash, from the bytes read before the walk (every lane; a match the
-    // walker extended is rehashed in walk_publish): independent of the scan below, so it
-    // fills the scan's DPP wait states.  (No early exit for a chunk a match from earlier
-    // chunks covers: it has no members, nothing is walked, the anchor stays.)
-    if constexpr (!kAllPos) O.e2h = hashk(O.e2v.x, O.e2v.y);
-    // catch-up limits: a member's backward extension stops at the previous end
+    // catch-up limits: a member's backward extension stops at the previous end.  (No early
+    // exit for a chunk a match from earlier chunks covers: it has no members, the anchor stays.)
     const uint32_t anchor0 = W.anchor;
     const bool mem = lane_in(O.members);
     const uint32_t p = P + (uint32_t)lane;
     uint32_t pm, lastend;
-    if constexpr (kWalkPm && !ACC) {   // (member lanes only: the others' limit is unused)
+    if constexpr (!ACC) {   // from the hop chain (member lanes only: the others' is unused)
         pm = P + O.pmv;
         lastend = P + O.pe;
     } else {
@@ -1030,47 +835,20 @@ __device__ __forceinline__ void walk_finish(const Blk &B, int k, int lane, Walk 
     O.m_back = bk;
     O.m_len = O.Lf + bk;
     O.an = pm;
-    // walked = every position from the walk start that no match of this chunk covers
-    // (with acceleration: the probed ones, every stride-th from the last match end)
-    bool w = p >= umax(O.q0, pm);
-    if (ACC) {   // the probed ones (the origin: the last match end before the lane)
-        const Probe R = probe_regime(P, anchor0, B.stride);
-        w = w && probed(p - pm, pm == anchor0, R, B.stride);
-    }
-    O.walked = wave_ballot(w);
     W.anchor = lastend;
 }
 
 __device__ __forceinline__ void walk_publish(EncLds &S, const Blk &B, int k, int lane,
-                                             const WalkOut &O, uint32_t &qn, int step) {
+                                             const WalkOut &O, uint32_t &qn) {
     const uint32_t p = 64u * (uint32_t)k + (uint32_t)lane;
     const uint2 iv = O.iv;
     const bool mem = lane_in(O.members);
-    if constexpr (!kAllPos) {   // (kAllPos: the producer has inserted every position)
-    if (lane_in(O.walked) && (iv.x & I_HASHABLE)) S.tab[iv.y >> 16] = (uint16_t)p;
-    const uint32_t fwd = O.m_len - O.m_back;      // match length from p
-    // match_end - 2 (:680) of the members, hashed here (off the producer's chain): from the
-    // ring bytes read before the walk, or, for a match the walker extended, from the input
-    const uint32_t e2 = p + fwd - 2u;
-    const bool e2ok = mem && e2 + 5u <= B.un;
-    uint32_t e2h = O.e2h;   // (ring bytes read before the walk: -1.6 % encode time)
-    if (e2ok && (iv.x & I_TRUNC)) {   // rare: a match the walker extended
-        uint32_t w[2] = {0u, 0u};   // in[e2, e2 + 8), 0 past the block end (as A loads it)
-        for (uint32_t t = 0; t < 8u; t++)
-            if (e2 + t < B.un) w[t >> 2] |= (uint32_t)B.in[e2 + t] << (8 * (t & 3));
-        e2h = hashk(w[0], w[1]);
-    }
-    // one wave's LDS operations complete in order: the walked-position inserts above
-    // land before these (compiler barrier only)
-    __builtin_amdgcn_sched_barrier(0);
-    if (e2ok) S.tab[e2h] = (uint16_t)e2;
-    }
     // the chunk's sequences, in order, as records for the emitter: literals from the
     // anchor to the match start (after catch-up), the match length and its offset
     if (mem) S.q[(qn + lane_rank(O.members)) & (kQ - 1u)] =
         make_uint2(((p - O.m_back) - O.an) | ((O.m_len - kMinMatch) << 16), iv.y & 0xFFFFu);
     qn += (uint32_t)__popcll(O.members);
-    if (lane == 0) S.qn[kOneBar ? (step & 1) : 0] = qn;
+    if (lane == 0) S.qn[0] = qn;
 }
 
 // ---------------- emitter ----------------
@@ -1295,11 +1073,12 @@ __device__ __forceinline__ void prefix_history(EncLds &S, const Blk &B, int lane
 
 // ---------------- block ----------------
 // Three waves per block, one role each, in lock step (two barriers per step):
-//   step s, first half : producer A(s+3) B(s+2) C1(s+1) | walker walks s-1 | emitter writes
-//                                                         |   the pair (s-4, s-3) (every 2nd step)
-//   step s, second half: producer C2(s) -> info     | walker inserts s-1, publishes
-//                                                         | emitter sizes s-2
-// Table inserts (second half) never overlap the producer's lookups (first half).
+//   step s, first half : producer R(s+2) B(s+2) A(s+4) C1(s+1) | walker walks s-1
+//                        | emitter fetches a batch of records or stages a piece of one
+//   step s, second half: producer S2(s+1) C2(s) -> info       | walker publishes s-1
+//                        | emitter stages the literals or stores the staged batch
+// Only the producer touches the table.  The mid-step barrier separates the walker's read of
+// info (chunk s-1) from the producer's write of it (chunk s).
 template <bool SMALL, bool ACC>
 __device__ __forceinline__ void encode_block(EncLds &S, const Blk &B, int wave, int lane,
                                              int *result, int *tail) {
@@ -1318,8 +1097,7 @@ __device__ __forceinline__ void encode_block(EncLds &S, const Blk &B, int wave, 
             // Every stage runs on every step, past the last chunk too (it then loads
             // from the block start and records nothing), so the number of loads per
             // step -- and with it the waits -- is the same on every path.
-            // In flight, oldest first: A(s+2), Y(s+1), A(s+3), E(s) -> A(s+2) at 3 (APF; without:
-            // A(s+2), Y(s+1), E(s)).
+            // In flight, oldest first: A(s+2), Y(s+1), A(s+3), E(s) -> A(s+2) at 3
             vm_wait<3>();
             STAT(9);   // (stats build: load waits)
             // ring copy of chunk s+2 (loaded a step ago), then C1(s+1)'s own bytes (chunks
@@ -1329,30 +1107,24 @@ __device__ __forceinline__ void encode_block(EncLds &S, const Blk &B, int wave, 
             prod_ring<F>(S, B, s + 2, lane, cur.X);
             uint32_t X6[6];   // C1(s+1)'s own bytes: in the ring since last step, read first
             prod_own(S, s + 1, lane, X6);
-#if APE_LZ4_APF
             prod_lookup<SMALL, F>(S, B, s + 2, lane, cur.X, cur.cT, cur.jL, cur.h, cur.Y);
             // A two steps ahead, into the set B(s+2) has just consumed: the block's own input
             // streams in from HBM, and one step (~1 us) did not cover it (the producer's load
             // waits were the A load at the step start)
             prod_load<SMALL, F>(B, s + 4, lane, cur.X);
             // Y(s+1), A(s+3), E(s), Y(s+2), A(s+4) -> Y(s+1) at 4
-#else
-            prod_load<SMALL, F>(B, s + 3, lane, nxt.X);
-            prod_lookup<SMALL, F>(S, B, s + 2, lane, cur.X, cur.cT, cur.jL, cur.h, cur.Y);
-            // Y(s+1) x2, E(s), A(s+3), Y(s+2) x2 -> Y(s+1) at 4
-#endif
             STAT(5);
             vm_wait<4>();
             STAT(9);
             prod_measure<SMALL, F>(S, B, s + 1, lane, X6, nxt.Y, nxt.cT, nxt.jL, nxt.h, nxt.q);
             STAT(5);
-            if constexpr (!kOneBar) __syncthreads();
+            __syncthreads();
             STAT(6);
             prod_stage2_issue<SMALL, F>(S, B, s + 1, lane, nxt.q, nxt.E);
             // E(s), A(s+3), Y(s+2) x2, E(s+1) -> E(s) at 4 (A(s+3), issued half a step ago,
             // is not needed before the next step)
             STAT(7);
-            vm_wait<(APE_LZ4_APF ? 3 : 4)>();   // (APF: Y(s+2), A(s+4), E(s+1) after E(s))
+            vm_wait<3>();   // (Y(s+2), A(s+4), E(s+1) after E(s))
             STAT(9);
             prod_finish<SMALL, F>(S, B, s, lane, cur.q, cur.E);
             STAT(7);
@@ -1368,7 +1140,7 @@ __device__ __forceinline__ void encode_block(EncLds &S, const Blk &B, int wave, 
             prod_load<SMALL>(B, k0 + 2, lane, P0.X);
             prod_ring(S, B, k0 + 1, lane, P1.X);
             prod_lookup<SMALL>(S, B, k0 + 1, lane, P1.X, P1.cT, P1.jL, P1.h, P1.Y);
-            if (APE_LZ4_APF) prod_load<SMALL>(B, k0 + 3, lane, P1.X);   // (step k0 + 1's X)
+            prod_load<SMALL>(B, k0 + 3, lane, P1.X);   // (step k0 + 1's X)
             prod_ring(S, B, k0 + 2, lane, P0.X);
             uint32_t X6[6];
             prod_own(S, k0, lane, X6);
@@ -1379,18 +1151,14 @@ __device__ __forceinline__ void encode_block(EncLds &S, const Blk &B, int wave, 
         // on its own issue order (once per block)
         __builtin_amdgcn_s_waitcnt(0);
         __syncthreads();
-        // Steps whose three loads all lie inside the block (A(s+3): 64(s+3)+72 <= n,
+        // Steps whose three loads all lie inside the block (A(s+4): 64(s+4)+72 <= n,
         // Y(s+2): 64(s+2)+83, E(s+1): 64(s+1)+148) run a loop without the edge paths;
-        // the last few steps run the general one.
-        // (APF: A(s+4), 64(s+4)+72 <= n)
-        constexpr int kFastEnd = APE_LZ4_APF ? 328 : 264;
+        // the last few steps run the general one.  A's bound is the tightest: n >= 64 s + 328
+        constexpr int kFastEnd = 328;
         const int nfast_abs = SMALL ? 0 : (int)umin((uint32_t)(B.n >= kFastEnd ? (B.n - kFastEnd) / 64 + 1 : 0),
                                                     (uint32_t)nsteps);
         const int nfast = nfast_abs > k0 ? k0 + ((nfast_abs - k0) & ~1) : k0;
         int s = k0;
-#ifdef APE_EXP_PUNROLL
-#pragma unroll APE_EXP_PUNROLL
-#endif
         for (; s < nfast; s += 2) {   // no conditional step: see pstep
             pstep(std::true_type{}, s, P0, P1);
             pstep(std::true_type{}, s + 1, P1, P0);
@@ -1414,18 +1182,15 @@ __device__ __forceinline__ void encode_block(EncLds &S, const Blk &B, int wave, 
         // the walking loop carries no per-step predicate)
         const int s2 = nch + 1;
         __syncthreads();   // step k0
-        if constexpr (!kOneBar) __syncthreads();
+        __syncthreads();
         int s = k0 + 1;
-#ifdef APE_EXP_WUNROLL
-#pragma unroll APE_EXP_WUNROLL
-#endif
         for (; s < s2; s++) {
             walk_chain<ACC>(S, B, s - 1, lane, W, O);
             STAT(0);
-            if constexpr (!kOneBar) __syncthreads();
+            __syncthreads();
             STAT(4);
             walk_finish<ACC>(B, s - 1, lane, W, O);
-            walk_publish(S, B, s - 1, lane, O, qn, s);
+            walk_publish(S, B, s - 1, lane, O, qn);
             STAT_ADD(11, __popcll(O.members));
             STAT(1);
             STAT_ADD(10, 3);
@@ -1434,7 +1199,7 @@ __device__ __forceinline__ void encode_block(EncLds &S, const Blk &B, int wave, 
         }
         for (; s < nsteps; s++) {
             __syncthreads();
-            if constexpr (!kOneBar) __syncthreads();
+            __syncthreads();
         }
         STATS_FLUSH(g_enc_stats);
         return;
@@ -1455,13 +1220,12 @@ __device__ __forceinline__ void encode_block(EncLds &S, const Blk &B, int wave, 
     E.r = E.lit = E.mlm4 = E.off = E.ba = 0;
     __syncthreads();
     for (int s = k0; s < nsteps; s++) {
-        // the walker's count as of its last publish before the previous barrier (kOneBar: its
-        // publish in step s - 1, by parity -- a step without a publish leaves the parity two
-        // steps old, smaller than what may be consumed already: clamped, so never negative)
-        const uint32_t qr = (uint32_t)__builtin_amdgcn_readfirstlane(kOneBar ? S.qn[(s - 1) & 1] : S.qn[0]);
+        // the walker's count as of its last publish before the previous barrier (clamped, so
+        // never negative)
+        const uint32_t qr = (uint32_t)__builtin_amdgcn_readfirstlane(S.qn[0]);
         const uint32_t avail = umax(qr, E.qc) - E.qc;
         if (E.pend == 0) {
-            if (avail != 0u && (avail >= kFetchAt || s - E.last >= APE_EMIT_EVERY)) {
+            if (avail != 0u && (avail >= kFetchAt || s - E.last >= kEmitEvery)) {
                 // piece L runs in the second half of step s, when the ring holds input
                 // [64 (s - 13), 64 (s + 3)) (chunk s + 2 was written over s - 14 at the
                 // start of step s; s + 3 overwrites s - 13 at the start of step s + 1)
@@ -1474,7 +1238,7 @@ __device__ __forceinline__ void encode_block(EncLds &S, const Blk &B, int wave, 
             emit_step(S, B, lane, E);
         }
         STAT(2);
-        if constexpr (!kOneBar) __syncthreads();
+        __syncthreads();
         STAT(14);
         if (E.pend == 1 || E.pend == 3) emit_step(S, B, lane, E);   // L or C
         STAT(12);
@@ -1486,7 +1250,9 @@ __device__ __forceinline__ void encode_block(EncLds &S, const Blk &B, int wave, 
     emit_all(S, B, lane, E);
     {
         const uint32_t rlo = B.nch > 16 ? 64u * (uint32_t)(B.nch - 16) : 0u;
-        // (counts only grow: the later of the two parities is the larger)
+        // (the max with the always-zero qn[1] is a remnant of a one-barrier variant; reading
+        // qn[0] alone reorders two instructions of the walker's step loop, see
+        // profiles/encoder_strip_asm_diff.txt, so it leaves in a change that is measured)
         for (uint32_t left = (uint32_t)__builtin_amdgcn_readfirstlane(umax(S.qn[0], S.qn[1])) - E.qc; left;) {
             const uint32_t qc0 = E.qc;
             emit_fetch(S, B, lane, E, left, rlo);
@@ -1528,7 +1294,7 @@ __device__ __forceinline__ void encode_block(EncLds &S, const Blk &B, int wave, 
 // ACC: compress_fast with acceleration > 1 (its own instantiation, so the default
 // kernel carries none of the probe-pattern code)
 template <bool ACC>
-__global__ void __launch_bounds__(192) __attribute__((amdgpu_waves_per_eu(APE_LZ4_WAVES_PER_EU)))
+__global__ void __launch_bounds__(192) __attribute__((amdgpu_waves_per_eu(kWavesPerEu)))
 lz4_encode_kernel(BlockArgs a) {
     __shared__ EncLds S;
     const int b = blockIdx.x;
@@ -1559,7 +1325,6 @@ lz4_encode_kernel(BlockArgs a) {
     B.nr = (uint32_t)nr;
     B.k0 = D / 64;
     // compress_fast's acceleration (:789-808): the reference's probe pattern (walk_chain)
-    B.noL = ACC && !APE_LZ4_ACC_L;
     B.stride = ACC ? (a.accel < (1 << 20) ? (uint32_t)a.accel : 1u << 20) : 1u;
     B.cap = (uint32_t)icap;
     B.un = (uint32_t)B.n;
@@ -1569,9 +1334,6 @@ lz4_encode_kernel(BlockArgs a) {
 
     // table = 0 (the reference's memset state: position 0 for every hash)
     for (int i = tid; i < kHSize / 8; i += 192) ((uint4 *)S.tab)[i] = make_uint4(0, 0, 0, 0);
-#if !APE_LZ4_NOL
-    for (int i = tid; i < (int)kScr; i += 192) S.scr[i] = 0xFFFFFFFFu;
-#endif
     for (int i = tid; i < (int)(kRingE / 16 + 4); i += 192) ((uint4 *)S.ring)[i] = make_uint4(0, 0, 0, 0);
     if (tid == 0) S.qn[0] = S.qn[1] = 0u;
     __syncthreads();

@@ -249,8 +249,9 @@ def test_acceleration(cuda, product, oracle):
     print("ratio by acceleration", {a: round(r, 4) for a, r in ratio.items()},
           "reference", {a: round(r, 4) for a, r in ref.items()})
     assert ratio[1] >= ratio[2] > ratio[4] > ratio[8] > ratio[1 << 30]
-    # one-sided: the GPU's 6-byte key and near candidate compress App. C data better than
-    # the reference's search (round 6: +7 % at a = 1); a ratio 1 % below the reference's fails
+    # one-sided: the GPU's 7-byte key over every position (no in-chunk candidate) compresses
+    # App. C data better than the reference's search (round 6: +7 % at a = 1); a ratio 1 %
+    # below the reference's fails
     for a in (1, 2, 4, 8):
         assert ratio[a] >= (1.0 - ACCEL_RATIO_TOL) * ref[a], (a, ratio[a], ref[a])
     # a huge acceleration probes only the three positions after each match end (and the

@@ -1,7 +1,10 @@
 #!/bin/bash
 # Build an encoder-only diagnostic variant: lz4_encode.hip with extra -D flags, linked with
 # the product's other objects -> libapenetwork_amd/libape_lz4_amd_<name>.so (never the product).
-# usage: bash tools/enc_variant.sh NAME "-DAPE_LZ4_..." [encoder source]
+# usage: bash tools/enc_variant.sh NAME "-D..." [encoder source]
+# The encoder's experiment flags (-DAPE_LZ4_HKEY=, _NOL=, _ONEBAR=, ...) exist in the source up to
+# commit 874a8fb only: git show 874a8fb:libapenetwork_amd/csrc/lz4_encode.hip > FILE, and pass FILE
+# as the encoder source ("Dead variants removed").
 set -e
 cd "$(dirname "$0")/.."
 V=$1; DEFS=$2; SRC=${3:-libapenetwork_amd/csrc/lz4_encode.hip}
