@@ -29,6 +29,10 @@
  * points give a larger input d_result = APE_LZ4_GPU_ERANGE.  Larger inputs, up to
  * 0x7E000000 bytes, go through APE_LZ4_compress_large_batch_dev, which compresses slices
  * in parallel and stitches them into one block.  The decoder has no block-size limit.
+ *
+ * History: compress_withPrefix takes it from the bytes before each input (chained streams);
+ * compress_usingCDict takes it from one prepared dictionary shared by the whole batch
+ * (independent messages); decompress_safe_usingDict decodes both.
  */
 #pragma once
 #include <stddef.h>
@@ -116,6 +120,52 @@ int APE_LZ4_decompress_safe_usingDict_batch_dev(const char *const *d_src,
                                                 const int *d_maxDecompressedSize,
                                                 const char *const *d_dict, const int *d_dictSize,
                                                 int *d_result, int nblocks, void *stream);
+
+/* ---- prepared dictionaries: many independent messages against one shared dictionary ----
+ * compress_withPrefix needs the history to be the bytes right before each input, which fits
+ * a chained stream.  The other classic use -- small independent messages (JSON frames, RPC
+ * replies) compressed against one shared dictionary, loadDict + compress_fast_continue on a
+ * fresh stream per message (ref src/ape_lz4.c:1101-1133, :1160-1220) -- goes through a
+ * PREPARED dictionary (in the sense of zstd's CDict): one kernel turns the dictionary into a
+ * device object holding a padded copy of the dictionary's tail and a prebuilt image of the
+ * encoder's hash table, and any number of later batched calls encode against it without a
+ * per-message copy or a per-message hashing pass.
+ *
+ * cdict_size    : bytes of device memory one prepared dictionary takes (a compile-time
+ *   constant, a multiple of 16).
+ * cdict_window  : bytes D of the dictionary's tail a prepared dictionary uses: D =
+ *   min(dictSize, 65536 - maxSrcSize) rounded down to a multiple of 64, below 64 -> 0.
+ *   Host-only arithmetic; -1 for arguments out of range.
+ * cdict_prepare : d_dict[dictSize - D, dictSize) -> the object at d_cdict (16-byte aligned,
+ *   cdict_bytes >= cdict_size()).  maxSrcSize (1..65536) trades dictionary for message size:
+ *   window and message share the encoder's one 64 KiB window.  dictSize may exceed 65536
+ *   (only the tail counts); dictSize 0 (d_dict may then be NULL), or a D that rounds to 0, is
+ *   legal and gives an object that encodes like APE_LZ4_compress_batch_dev, without history.
+ *   One asynchronous launch, no allocation, no sync, graph-capturable.  It writes EVERY byte
+ *   of d_cdict[0, cdict_size()), so two prepares of the same input give identical bytes.
+ * compress_usingCDict : == N x (loadDict(dict) ; compress_fast_continue(src, acceleration
+ *   1)) on fresh streams.  d_result[i] <- compressed size, or 0 if it does not fit
+ *   d_dstCap[i] or the size is negative; APE_LZ4_GPU_ERANGE when d_srcSize[i] exceeds the
+ *   maxSrcSize the object was prepared for.  The other blocks of the call are unaffected.
+ *   The output is a valid LZ4 block that decompress_safe_usingDict(src, dst, csize, cap,
+ *   dict, dictSize) decodes with the CALLER'S ORIGINAL dictionary (offsets count back from
+ *   its end, so any placement works); bytes differ from the reference's, as for every
+ *   GPU-compressed block.  A match taken from the dictionary ends at the dictionary's end
+ *   (the reference lets it run on into the message; a few bytes of ratio).
+ *   The object is only read: any number of calls, on any streams, may share it.  It starts
+ *   with a header (magic, D, maxSrcSize) that the kernel checks before it uses anything else
+ *   of it: every block of a call on an object that was never prepared gets result 0.  One
+ *   dictionary per call; no acceleration parameter (as compress_withPrefix has none).
+ * Both launchers return APE_LZ4_GPU_EINVAL before any device call for a null pointer,
+ * nblocks < 0, dictSize < 0, maxSrcSize out of range, cdict_bytes too small or d_cdict not
+ * 16-byte aligned; 0 otherwise. */
+size_t APE_LZ4_cdict_size(void);
+int APE_LZ4_cdict_window(int dictSize, int maxSrcSize);
+int APE_LZ4_cdict_prepare_dev(const char *d_dict, int dictSize, int maxSrcSize, void *d_cdict,
+                              size_t cdict_bytes, void *stream);
+int APE_LZ4_compress_usingCDict_batch_dev(const char *const *d_src, const int *d_srcSize,
+                                          char *const *d_dst, const int *d_dstCap, int *d_result,
+                                          int nblocks, const void *d_cdict, void *stream);
 
 /* == N x APE_LZ4_decompress_fast(src, dst, originalSize) (ref src/ape_lz4.c:1489):
  * d_result[i] <- compressed bytes consumed, or -(consumed)-1.  The reference reads its

@@ -25,6 +25,7 @@ __all__ = [
     "Chain",
     "compress_large_slice_size", "compress_large_scratch_size", "compress_large_ptr_batch",
     "oneshot_on_gpu",
+    "cdict_size", "cdict_window", "cdict_prepare", "compress_cdict_batch",
     "ONESHOT_HOST_ALL",
 ]
 
@@ -84,6 +85,10 @@ def lib():
             "APE_LZ4_compress_large_slice_size": (i, []),
             "APE_LZ4_compress_large_scratch_size": (sz, [i, i]),
             "APE_LZ4_compress_large_batch_dev": (i, [p, p, p, p, p, i, i, i, p, sz, p]),
+            "APE_LZ4_cdict_size": (sz, []),
+            "APE_LZ4_cdict_window": (i, [i, i]),
+            "APE_LZ4_cdict_prepare_dev": (i, [p, i, i, p, sz, p]),
+            "APE_LZ4_compress_usingCDict_batch_dev": (i, [p, p, p, p, p, i, p, p]),
             "APE_LZ4_rxbuf_new": (p, [sz]),
             "APE_LZ4_rxbuf_prepare": (i, [p, sz]),
             "APE_LZ4_rxbuf_append": (i, [p, p, sz]),
@@ -429,6 +434,45 @@ def compress_large_ptr_batch(src_ptrs, src_sizes, dst_ptrs, caps, results, max_s
         max_src_size, acceleration, _ptr(scratch), scratch.numel(), _stream(stream)),
         "APE_LZ4_compress_large_batch_dev")
     return scratch
+
+
+def cdict_size():
+    """APE_LZ4_cdict_size: bytes of device memory one prepared dictionary takes."""
+    return lib().APE_LZ4_cdict_size()
+
+
+def cdict_window(dict_size, max_src_size):
+    """APE_LZ4_cdict_window: bytes of the dictionary's tail a prepared dictionary uses."""
+    return lib().APE_LZ4_cdict_window(dict_size, max_src_size)
+
+
+def cdict_prepare(dict_tensor, max_src_size, cdict_tensor, stream=None):
+    """APE_LZ4_cdict_prepare_dev: dict_tensor (uint8 CUDA, any placement; may be empty) ->
+    the prepared dictionary in cdict_tensor (uint8 CUDA, >= cdict_size() bytes, 16-byte
+    aligned) for messages of up to max_src_size bytes.  Returns cdict_tensor."""
+    import torch
+    _arr(dict_tensor, "cdict_prepare dict", torch.uint8)
+    _arr(cdict_tensor, "cdict_prepare cdict", torch.uint8)
+    _check(lib().APE_LZ4_cdict_prepare_dev(
+        _ptr(dict_tensor) if dict_tensor.numel() else None, dict_tensor.numel(), max_src_size,
+        _ptr(cdict_tensor), cdict_tensor.numel(), _stream(stream)), "APE_LZ4_cdict_prepare_dev")
+    return cdict_tensor
+
+
+def compress_cdict_batch(src_ptrs, src_sizes, dst_ptrs, caps, results, cdict, stream=None):
+    """N x (loadDict ; compress_fast_continue) against one prepared dictionary (cdict_prepare);
+    pointer-array form (int64 tensors of pointers)."""
+    import torch
+    _arr(src_sizes, "compress_cdict_batch src_sizes", torch.int32)
+    n = src_sizes.shape[0]
+    _ptr_args("compress_cdict_batch", n, src_ptrs=(src_ptrs, _i64()), src_sizes=(src_sizes, _i32()),
+              dst_ptrs=(dst_ptrs, _i64()), caps=(caps, _i32()), results=(results, _i32()))
+    _arr(cdict, "compress_cdict_batch cdict", torch.uint8)
+    if cdict.numel() < cdict_size():
+        raise ValueError("compress_cdict_batch cdict: smaller than cdict_size()")
+    _check(lib().APE_LZ4_compress_usingCDict_batch_dev(
+        _ptr(src_ptrs), _ptr(src_sizes), _ptr(dst_ptrs), _ptr(caps), _ptr(results), n,
+        _ptr(cdict), _stream(stream)), "APE_LZ4_compress_usingCDict_batch_dev")
 
 
 def decompress_dict_batch(src_ptrs, comp_sizes, dst_ptrs, caps, dict_ptrs, dict_sizes, results,

@@ -58,17 +58,9 @@ hipError_t enc_stats_read(unsigned long long *out, int reset) {
 
 namespace {
 
-// Table entries, the hash scaled onto [0, kHSize).  7328 entries make the block's LDS 17904
-// bytes, inside the 35 x 512-byte granules that fit 9 blocks = 27 waves per CU (7 per SIMD:
-// <= 72 VGPRs); the reference's 8192 entries fit 8 blocks, +4.6 % encode time for +0.6 % ratio
-// (measured; tools/enc_model.c models the ratio per table size).
-constexpr int kHSize = 7328;
-static_assert(kHSize < 8192 && kHSize % 8 == 0, "table size");
-constexpr int kWavesPerEu = 7;       // (amdgpu_waves_per_eu: the register budget that goes with it)
-// Bytes the table hash covers (the reference: 5, :456-473).  7 keeps short chance matches from
-// pre-empting longer ones: ratio up, 23 % fewer sequences (tools/enc_model.c key study,
-// DESIGN.md 3.1).
-constexpr int kKey = 7;
+// (kHSize, kKey and hashk: lz4_gpu_internal.h, shared with the prepared dictionary's table image)
+constexpr int kWavesPerEu = 7;       // (amdgpu_waves_per_eu: the register budget that goes with
+                                     // kHSize's 9 blocks per CU)
 // Table inserts: the producer writes every hashable position of a chunk into the table right
 // after the chunk's lookups, so chunk k sees every position of chunks < k, and the walker
 // inserts nothing.  No in-chunk candidate beside the table's.  (The reference's insert policy,
@@ -212,20 +204,6 @@ __device__ __forceinline__ void load32(gcu8 *in, int n, int pos, uint32_t (&X)[8
     }
 }
 
-// Hash of the kKey bytes at p (x0 = in[p..p+3], x1 = in[p+4..p+7]) onto [0, kHSize).  The
-// reference multiplies the 40-bit sequence by 889523592379 (:456-473), which needs
-// quarter-rate 32-bit multiplies here; any hash gives a valid stream, so this one uses
-// full-rate 24 x 24-bit multiplies (v_mul_u32_u24 / v_mad_u32_u24, which read only the low
-// 24 bits of their operands) of bytes 0-2, 3-5 and 6.
-__device__ __forceinline__ uint32_t hashk(uint32_t x0, uint32_t x1) {
-    static_assert(kKey == 7, "hashk covers bytes 0..6");
-    const uint32_t hi = __builtin_amdgcn_alignbyte(x1, x0, 3u);   // bytes 3..6 (the multiply takes 3..5)
-    // (__umul24 returns int: do the sums unsigned)
-    const uint32_t v = (uint32_t)__umul24(x0, 0x9E3779u) + (uint32_t)__umul24(hi, 0xC2B2AEu) +
-                       (uint32_t)__umul24((x1 >> 16) & 0xFFu, 0x27D4EBu);
-    return __umulhi(v, (uint32_t)kHSize);   // v scaled onto [0, kHSize): one v_mul_hi_u32
-}
-
 // v_ffbl_b32 / v_ffbh_u32: lowest / highest set bit, 0xFFFFFFFF for 0 (inline asm
 // so that the compiler does not turn the zero case into compare + select)
 __device__ __forceinline__ uint32_t ffbl(uint32_t d) {
@@ -355,7 +333,40 @@ struct Blk {
                                      // history prefix (withPrefix encode), only hashed
     uint32_t nr;                     // bytes to encode (n - 64 k0)
     uint32_t stride;                 // acceleration (compress_fast): the first search step
+    gcu8 *win;                       // EXT only: the prepared dictionary's window, positions
+    uint32_t D;                      // [0, D) (= 64 k0); `in` + pos is memory for pos >= D only
 };
+
+// EXT (encode against a prepared dictionary, APE_LZ4_compress_usingCDict_batch_dev): the
+// history [0, D) does not lie before the block but in the object's window.  Every load of
+// history goes through this one address select -- also the loads of lanes that have nothing
+// to load and fall back to position 0, which is not memory here.  A 16-byte load that starts
+// below D never continues into the block: it reads the window's pad, so whatever a candidate
+// below D measures is cut at D (prod_measure, extend_match).
+template <bool EXT>
+__device__ __forceinline__ gcu8 *hist(const Blk &B, uint32_t pos) {
+    if constexpr (EXT) return pos < B.D ? B.win + pos : B.in + pos;
+    else return B.in + pos;
+}
+// loadv of history
+template <bool EXT, int NA>
+__device__ __forceinline__ void loadv_h(const Blk &B, uint32_t pos, uint32_t (&X)[NA], bool fast) {
+    if constexpr (!EXT) {
+        loadv(B.in, B.un, pos, X, fast);
+    } else {
+        gcu8 *q = hist<true>(B, pos);
+        if (fast) {
+            const uint4 a = gload16(q);
+            X[0] = a.x; X[1] = a.y; X[2] = a.z; X[3] = a.w;
+            return;
+        }
+#pragma unroll
+        for (int k = 0; k < 4; k++) X[k] = 0;
+#pragma unroll
+        for (uint32_t t = 0; t < 16u; t++)
+            if (pos + t < B.un) X[t >> 2] |= (uint32_t)q[t] << (8 * (t & 3));
+    }
+}
 
 // ---------------- producer ----------------
 struct Part {                        // C1 result of one chunk, finished by C2
@@ -382,9 +393,10 @@ struct PSet {
 };
 
 // A(k): own bytes in[p, p+8) for the hash (0 past the block end)
-template <bool SMALL, bool FAST = false>
+template <bool SMALL, bool FAST = false, bool EXT = false>
 __device__ __forceinline__ void prod_load(const Blk &B, int k, int lane, uint32_t (&X)[2]) {
-    const uint32_t pos = (FAST || k < B.nch ? 64u * (uint32_t)k : 0u) + (uint32_t)lane;
+    // (EXT: a lane past the last chunk loads from the block's start, position D)
+    const uint32_t pos = (FAST || k < B.nch ? 64u * (uint32_t)k : (EXT ? B.D : 0u)) + (uint32_t)lane;
     if (FAST || (!SMALL && 64 * k + 72 <= B.n)) {   // wave-uniform: the whole window is inside
         const uint2 v = gload8(B.in + pos);
         X[0] = v.x;
@@ -400,21 +412,21 @@ __device__ __forceinline__ void prod_load(const Blk &B, int k, int lane, uint32_
 // T candidate bytes in[T-4, T+kEagerLen) of chunk k (issued one step before C1 consumes them).
 // Candidates below position 4 are skipped: their 4 bytes of backward context would start
 // before the block (never-written slots read as 0).
-template <bool SMALL, bool FAST = false>
+template <bool SMALL, bool FAST = false, bool EXT = false>
 __device__ __forceinline__ void prod_fetch_t(const Blk &B, int k, int lane, uint32_t cT,
                                              uint32_t (&Y)[6]) {
     const uint32_t p = 64u * (uint32_t)k + (uint32_t)lane;
     if (FAST) {   // any address in [0, p): a lane whose T is not a candidate (C1 rechecks
                   // cT < p and cT >= 4) loads harmless bytes -- min + saturating subtract
-        loadv(B.in, B.un, __builtin_elementwise_sub_sat(umin(cT, p - 1u), 4u), Y, true);
+        loadv_h<EXT>(B, __builtin_elementwise_sub_sat(umin(cT, p - 1u), 4u), Y, true);
         return;
     }
     const bool tryT = k < B.nch && cT < p && cT >= 4u;
-    loadv(B.in, B.un, tryT ? cT - 4u : 0u, Y, !SMALL && 64 * k + 83 <= B.n);
+    loadv_h<EXT>(B, tryT ? cT - 4u : 0u, Y, !SMALL && 64 * k + 83 <= B.n);
 }
 
 // B(k): hash, table candidate T, table insert, T fetch issue
-template <bool SMALL, bool FAST = false>
+template <bool SMALL, bool FAST = false, bool EXT = false>
 __device__ __forceinline__ void prod_lookup(EncLds &S, const Blk &B, int k, int lane,
                                             const uint32_t (&X)[2], uint32_t &cT, uint32_t &jL,
                                             uint32_t &h, uint32_t (&Y)[6]) {
@@ -427,7 +439,7 @@ __device__ __forceinline__ void prod_lookup(EncLds &S, const Blk &B, int k, int 
     // after this chunk's lookups (one wave's LDS operations complete in order); lanes with
     // the same slot: the last lane's write lands last, the latest position wins
     if (hashable) S.tab[h] = (uint16_t)p;
-    prod_fetch_t<SMALL, FAST>(B, k, lane, cT, Y);
+    prod_fetch_t<SMALL, FAST, EXT>(B, k, lane, cT, Y);
 }
 
 // R(k): ring copy of chunk k (own bytes for C1 and stage 2, literals; zero
@@ -489,7 +501,7 @@ __device__ __forceinline__ uint32_t stage2_len(const EncLds &S, int lane, uint32
 
 // C1(k): verify the T candidate and measure it to kEagerLen bytes; mark the truncated lanes
 // and, of them, the ones stage 2 measures
-template <bool SMALL, bool FAST = false>
+template <bool SMALL, bool FAST = false, bool EXT = false>
 __device__ __forceinline__ void prod_measure(EncLds &S, const Blk &B, int k, int lane,
                                              const uint32_t (&X)[6], const uint32_t (&Y)[6],
                                              uint32_t cT, uint32_t jL, uint32_t h, Part &R) {
@@ -509,11 +521,16 @@ __device__ __forceinline__ void prod_measure(EncLds &S, const Blk &B, int k, int
     for (int t = 0; t < 4; t++) Z[t] = bperm(X[t], jL);
     constexpr bool okL = false;
     // (bitwise on bools: lane masks combined by the scalar unit, no materialised 0/1)
-    const bool okT = can & (cT < p) & (cT >= 4u) & (Y[1] == X[1]);
+    // EXT: the bytes of a candidate within 3 of D on either side were loaded across the
+    // window's end (its 4-byte verify, or its backward context, is pad): no candidate.  A
+    // candidate further below D matches at most up to D (R.lim, >= 4).
+    const bool okT = can & (cT < p) & (cT >= 4u) & (Y[1] == X[1]) & (!EXT | (cT + 3u - B.D > 6u));
     // (FAST: the match limit lies >= 132 bytes past every lane, beyond anything C1 and C2
     // measure, so it never cuts a length: no limit arithmetic at all)
     R.lim = FAST ? 0xFFFFu : (can ? B.mlimit - p : 0u);   // (a FAST chunk finished by a
                                                             // general step: no cut either)
+    // (EXT: the one limit a FAST chunk still has is a window candidate's cut at D)
+    if constexpr (EXT) R.lim = cT < B.D ? umin(R.lim, B.D - cT) : R.lim;
     // measured unconditionally (a select, no branch): every lane reads Y, so the
     // compiler sees the candidate load consumed on every path; C2 continues from where
     // C1 stopped
@@ -526,7 +543,7 @@ __device__ __forceinline__ void prod_measure(EncLds &S, const Blk &B, int k, int
     R.base = pickL ? kEagerL : kEagerLen;
     // (two ballots of compares fold into the compares; a ballot of their AND made the
     // compiler materialise a 0/1 and compare it again)
-    if (FAST) {
+    if (FAST && !EXT) {
         R.tmask = wave_ballot(R.len >= R.base);
     } else {
         R.tmask = wave_ballot(R.len >= R.base) & wave_ballot(R.lim > R.base);
@@ -545,7 +562,7 @@ __device__ __forceinline__ void prod_measure(EncLds &S, const Blk &B, int k, int
 
 // S2(k), at the start of the second half (off C1's latency chain, next to C2(k-1)):
 // rank the truncated lanes and issue the stage-2 loads of the first kGroups of them
-template <bool SMALL, bool FAST = false>
+template <bool SMALL, bool FAST = false, bool EXT = false>
 __device__ __forceinline__ void prod_stage2_issue(const EncLds &S, const Blk &B, int k, int lane,
                                                   Part &R, uint32_t (&E)[4]) {
     const uint32_t p = 64u * (uint32_t)k + (uint32_t)lane;
@@ -555,11 +572,11 @@ __device__ __forceinline__ void prod_stage2_issue(const EncLds &S, const Blk &B,
     uint32_t cb;
     const bool ga = stage2_group(R, lane, 0u, p, cb, R.eo);
     // cb + 16 <= c + base + kExt2 < p + 80 (c < p)
-    loadv(B.in, B.un, ga ? cb : 0u, E, FAST || (!SMALL && 64 * k + 148 <= B.n));
+    loadv_h<EXT>(B, ga ? cb : 0u, E, FAST || (!SMALL && 64 * k + 148 <= B.n));
 }
 
 // C2(k): finish the truncated lengths against the ring -> info
-template <bool SMALL, bool FAST = false>
+template <bool SMALL, bool FAST = false, bool EXT = false>
 __device__ __forceinline__ void prod_finish(EncLds &S, const Blk &B, int k, int lane,
                                             const Part &R, const uint32_t (&E)[4]) {
     const uint32_t p = 64u * (uint32_t)k + (uint32_t)lane;
@@ -570,15 +587,15 @@ __device__ __forceinline__ void prod_finish(EncLds &S, const Blk &B, int k, int 
         for (uint32_t first = kGroups; first < R.ntr; first += kGroups) {   // rare
             uint32_t cb, eo, E2[4];
             const bool ga = stage2_group(R, lane, first, p, cb, eo);
-            loadv(B.in, B.un, ga ? cb : 0u, E2, FAST || (!SMALL && 64 * k + 148 <= B.n));
+            loadv_h<EXT>(B, ga ? cb : 0u, E2, FAST || (!SMALL && 64 * k + 148 <= B.n));
             const uint32_t m2 = bperm(stage2_len(S, lane, eo, E2), 4u * (R.rank - first));
             if (R.rank - first < kGroups) mine = m2;
         }
         if (lane_in(R.tmask)) {
             // mine - p = the run's last lane's length + the distance to it
             const uint32_t cap = R.base + kExt2, full = mine - p;
-            len = FAST ? umin(full, cap) : umin(umin(full, cap), R.lim);
-            trunc = full >= cap && (FAST || R.lim > cap);
+            len = (FAST && !EXT) ? umin(full, cap) : umin(umin(full, cap), R.lim);
+            trunc = full >= cap && ((FAST && !EXT) || R.lim > cap);
         }
     }
     // (FAST: the chunk lies inside the block, every lane hashable -- also the prologue's
@@ -628,16 +645,18 @@ __device__ __forceinline__ bool probed(uint32_t d, bool far, const Probe &R, uin
 
 // forward extension of the match at m (candidate cm) from L bytes on, with the
 // whole wave, 1 KiB per step; returns the full length (<= mlimit - m)
+template <bool EXT = false>
 __device__ __forceinline__ uint32_t extend_match(const Blk &B, uint32_t m, uint32_t cm, uint32_t L,
                                                  int lane) {
-    const uint32_t lm = B.mlimit - m;
+    uint32_t lm = B.mlimit - m;
+    if constexpr (EXT) lm = cm < B.D ? umin(lm, B.D - cm) : lm;   // (a window match ends at D)
     for (;;) {
         const uint32_t kk = L + 16u * (uint32_t)lane;
         uint32_t d = 0, at = 0;
         if (kk < lm) {
             uint32_t xb[4] = {0, 0, 0, 0}, yb[4] = {0, 0, 0, 0};
             if (m + kk + 16u <= B.un) {
-                const uint4 x = gload16(B.in + (m + kk)), y = gload16(B.in + (cm + kk));
+                const uint4 x = gload16(B.in + (m + kk)), y = gload16(hist<EXT>(B, cm + kk));
                 xb[0] = x.x; xb[1] = x.y; xb[2] = x.z; xb[3] = x.w;
                 yb[0] = y.x; yb[1] = y.y; yb[2] = y.z; yb[3] = y.w;
             } else {
@@ -645,7 +664,7 @@ __device__ __forceinline__ uint32_t extend_match(const Blk &B, uint32_t m, uint3
                 for (uint32_t t = 0; t < 16u; t++) {
                     if (m + kk + t < B.un) {
                         xb[t >> 2] |= (uint32_t)B.in[m + kk + t] << (8 * (t & 3));
-                        yb[t >> 2] |= (uint32_t)B.in[cm + kk + t] << (8 * (t & 3));
+                        yb[t >> 2] |= (uint32_t)*hist<EXT>(B, cm + kk + t) << (8 * (t & 3));
                     }
                 }
             }
@@ -727,7 +746,7 @@ __device__ __forceinline__ void hop_chain(uint64_t Hm, uint32_t nxt, uint32_t &r
 
 // First half: the hop chain only (the latency-bound part); second half: the lane-parallel
 // catch-up limits and the anchor (walk_finish).
-template <bool ACC>
+template <bool ACC, bool EXT = false>
 __device__ __forceinline__ void walk_chain(const EncLds &S, const Blk &B, int k, int lane, Walk &W,
                                            WalkOut &O) {
     const uint32_t P = 64u * (uint32_t)k;
@@ -752,7 +771,7 @@ __device__ __forceinline__ void walk_chain(const EncLds &S, const Blk &B, int k,
         while (__builtin_expect(rel >= 256u, 0)) {   // unfinished (rare): the wave extends it
             const uint32_t me = P + j;
             const uint32_t cm = me - (lane_val(iv.y, (int)j) & 0xFFFFu);
-            const uint32_t Le = extend_match(B, me, cm, rel - 256u - j, lane);
+            const uint32_t Le = extend_match<EXT>(B, me, cm, rel - 256u - j, lane);
             if ((uint32_t)lane == j) O.Lf = Le;
             rel = j + Le;
             O.pe = rel;
@@ -782,7 +801,7 @@ __device__ __forceinline__ void walk_chain(const EncLds &S, const Blk &B, int k,
         if (h & 0x80u) {
             const uint32_t me = P + j;
             const uint32_t cm = me - (lane_val(iv.y, (int)j) & 0xFFFFu);
-            const uint32_t Le = extend_match(B, me, cm, h & 0x7Fu, lane);
+            const uint32_t Le = extend_match<EXT>(B, me, cm, h & 0x7Fu, lane);
             if ((uint32_t)lane == j) O.Lf = Le;
             rel = j + Le;
         } else {
@@ -1071,6 +1090,15 @@ __device__ __forceinline__ void prefix_history(EncLds &S, const Blk &B, int lane
     if (((D - 64u) & (kRingE - 1)) == 0u) ((uint8_t *)S.ring)[kRingE + lane] = by;
 }
 
+// EXT: the table already holds the prepared image (copied by the whole workgroup); only the
+// ring copy of the window's last 64 bytes is left
+__device__ __forceinline__ void cdict_history(EncLds &S, const Blk &B, int lane) {
+    const uint32_t p = B.D - 64u + (uint32_t)lane;
+    const uint8_t by = B.win[p];
+    ((uint8_t *)S.ring)[p & (kRingE - 1)] = by;
+    if (((B.D - 64u) & (kRingE - 1)) == 0u) ((uint8_t *)S.ring)[kRingE + lane] = by;
+}
+
 // ---------------- block ----------------
 // Three waves per block, one role each, in lock step (two barriers per step):
 //   step s, first half : producer R(s+2) B(s+2) A(s+4) C1(s+1) | walker walks s-1
@@ -1079,7 +1107,7 @@ __device__ __forceinline__ void prefix_history(EncLds &S, const Blk &B, int lane
 //                        | emitter stages the literals or stores the staged batch
 // Only the producer touches the table.  The mid-step barrier separates the walker's read of
 // info (chunk s-1) from the producer's write of it (chunk s).
-template <bool SMALL, bool ACC>
+template <bool SMALL, bool ACC, bool EXT = false>
 __device__ __forceinline__ void encode_block(EncLds &S, const Blk &B, int wave, int lane,
                                              int *result, int *tail) {
     STATS_DECL
@@ -1107,45 +1135,49 @@ __device__ __forceinline__ void encode_block(EncLds &S, const Blk &B, int wave, 
             prod_ring<F>(S, B, s + 2, lane, cur.X);
             uint32_t X6[6];   // C1(s+1)'s own bytes: in the ring since last step, read first
             prod_own(S, s + 1, lane, X6);
-            prod_lookup<SMALL, F>(S, B, s + 2, lane, cur.X, cur.cT, cur.jL, cur.h, cur.Y);
+            prod_lookup<SMALL, F, EXT>(S, B, s + 2, lane, cur.X, cur.cT, cur.jL, cur.h, cur.Y);
             // A two steps ahead, into the set B(s+2) has just consumed: the block's own input
             // streams in from HBM, and one step (~1 us) did not cover it (the producer's load
             // waits were the A load at the step start)
-            prod_load<SMALL, F>(B, s + 4, lane, cur.X);
+            prod_load<SMALL, F, EXT>(B, s + 4, lane, cur.X);
             // Y(s+1), A(s+3), E(s), Y(s+2), A(s+4) -> Y(s+1) at 4
             STAT(5);
             vm_wait<4>();
             STAT(9);
-            prod_measure<SMALL, F>(S, B, s + 1, lane, X6, nxt.Y, nxt.cT, nxt.jL, nxt.h, nxt.q);
+            prod_measure<SMALL, F, EXT>(S, B, s + 1, lane, X6, nxt.Y, nxt.cT, nxt.jL, nxt.h, nxt.q);
             STAT(5);
             __syncthreads();
             STAT(6);
-            prod_stage2_issue<SMALL, F>(S, B, s + 1, lane, nxt.q, nxt.E);
+            prod_stage2_issue<SMALL, F, EXT>(S, B, s + 1, lane, nxt.q, nxt.E);
             // E(s), A(s+3), Y(s+2) x2, E(s+1) -> E(s) at 4 (A(s+3), issued half a step ago,
             // is not needed before the next step)
             STAT(7);
             vm_wait<3>();   // (Y(s+2), A(s+4), E(s+1) after E(s))
             STAT(9);
-            prod_finish<SMALL, F>(S, B, s, lane, cur.q, cur.E);
+            prod_finish<SMALL, F, EXT>(S, B, s, lane, cur.q, cur.E);
             STAT(7);
             __syncthreads();
             STAT(8);
         };
-        if (k0 > 0) prefix_history(S, B, lane);
+        if constexpr (EXT) {
+            if (k0 > 0) cdict_history(S, B, lane);
+        } else {
+            if (k0 > 0) prefix_history(S, B, lane);
+        }
         if (nch > k0) {  // prologue: A(k0), A(k0+1), B(k0), A(k0+2), B(k0+1), C1(k0)
-            prod_load<SMALL>(B, k0, lane, P0.X);
-            prod_load<SMALL>(B, k0 + 1, lane, P1.X);
+            prod_load<SMALL, false, EXT>(B, k0, lane, P0.X);
+            prod_load<SMALL, false, EXT>(B, k0 + 1, lane, P1.X);
             prod_ring(S, B, k0, lane, P0.X);
-            prod_lookup<SMALL>(S, B, k0, lane, P0.X, P0.cT, P0.jL, P0.h, P0.Y);
-            prod_load<SMALL>(B, k0 + 2, lane, P0.X);
+            prod_lookup<SMALL, false, EXT>(S, B, k0, lane, P0.X, P0.cT, P0.jL, P0.h, P0.Y);
+            prod_load<SMALL, false, EXT>(B, k0 + 2, lane, P0.X);
             prod_ring(S, B, k0 + 1, lane, P1.X);
-            prod_lookup<SMALL>(S, B, k0 + 1, lane, P1.X, P1.cT, P1.jL, P1.h, P1.Y);
-            prod_load<SMALL>(B, k0 + 3, lane, P1.X);   // (step k0 + 1's X)
+            prod_lookup<SMALL, false, EXT>(S, B, k0 + 1, lane, P1.X, P1.cT, P1.jL, P1.h, P1.Y);
+            prod_load<SMALL, false, EXT>(B, k0 + 3, lane, P1.X);   // (step k0 + 1's X)
             prod_ring(S, B, k0 + 2, lane, P0.X);
             uint32_t X6[6];
             prod_own(S, k0, lane, X6);
-            prod_measure<SMALL>(S, B, k0, lane, X6, P0.Y, P0.cT, P0.jL, P0.h, P0.q);
-            prod_stage2_issue<SMALL>(S, B, k0, lane, P0.q, P0.E);
+            prod_measure<SMALL, false, EXT>(S, B, k0, lane, X6, P0.Y, P0.cT, P0.jL, P0.h, P0.q);
+            prod_stage2_issue<SMALL, false, EXT>(S, B, k0, lane, P0.q, P0.E);
         }
         // nothing in flight at the loop entry, so the loop's counter waits depend only
         // on its own issue order (once per block)
@@ -1185,7 +1217,7 @@ __device__ __forceinline__ void encode_block(EncLds &S, const Blk &B, int wave, 
         __syncthreads();
         int s = k0 + 1;
         for (; s < s2; s++) {
-            walk_chain<ACC>(S, B, s - 1, lane, W, O);
+            walk_chain<ACC, EXT>(S, B, s - 1, lane, W, O);
             STAT(0);
             __syncthreads();
             STAT(4);
@@ -1340,6 +1372,63 @@ lz4_encode_kernel(BlockArgs a) {
     int *const tail = a.tail ? a.tail + b : nullptr;
     if (B.n < kSmall) encode_block<true, ACC>(S, B, wave, lane, &a.result[b], tail);
     else encode_block<false, ACC>(S, B, wave, lane, &a.result[b], tail);
+}
+
+// EXT: N x (loadDict ; compress_fast_continue) against one prepared dictionary (layout:
+// lz4_gpu_internal.h).  The block's positions are [D, D + nr) of one 64 KiB window whose
+// [0, D) is the object's window; the table starts as the object's image instead of zero, so
+// no block hashes the dictionary.  The object is only read.
+__global__ void __launch_bounds__(192) __attribute__((amdgpu_waves_per_eu(kWavesPerEu)))
+lz4_encode_cdict_kernel(BlockArgs a, const uint8_t *cd) {
+    __shared__ EncLds S;
+    const int b = blockIdx.x;
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+
+    // the header first: nothing else of an object that fails this is read
+    const CDictHdr H = *(const CDictHdr *)cd;
+    if (H.magic != kCdMagic || H.D > kCdMaxWin || (H.D & 63u) != 0u || H.max_src < 1u ||
+        H.max_src > (uint32_t)kMaxBlock || H.D + H.max_src > (uint32_t)kMaxBlock) {
+        if (tid == 0) a.result[b] = 0;
+        return;
+    }
+    const int nr = a.src_size[b];
+    const int icap = a.dst_cap[b];
+    if (nr < 0 || nr > (int)H.max_src || icap < 0) {
+        if (tid == 0) a.result[b] = (nr > (int)H.max_src) ? kErange : 0;
+        return;
+    }
+    const int D = (int)H.D;
+    Blk B;
+    B.win = (gcu8 *)(cd + kCdWin + kCdFront);
+    B.D = (uint32_t)D;
+    B.in = (gcu8 *)a.src[b] - D;     // (an address only: nothing below position D is read from it)
+    B.dst = (gu8 *)a.dst[b];
+    B.n = D + nr;
+    B.nr = (uint32_t)nr;
+    B.k0 = D / 64;
+    B.stride = 1u;
+    B.cap = (uint32_t)icap;
+    B.un = (uint32_t)B.n;
+    B.mstart = B.un >= 12 ? B.un - 12 : 0;
+    B.mlimit = B.un >= 5 ? B.un - 5 : 0;
+    B.nch = (B.n + 63) / 64;
+
+    // table = the prepared image (all zero for D = 0: the state of a block without history)
+    const uint4 *img = (const uint4 *)(cd + kCdTab);
+    for (int i = tid; i < kHSize / 8; i += 192) ((uint4 *)S.tab)[i] = img[i];
+    for (int i = tid; i < (int)(kRingE / 16 + 4); i += 192) ((uint4 *)S.ring)[i] = make_uint4(0, 0, 0, 0);
+    if (tid == 0) S.qn[0] = S.qn[1] = 0u;
+    __syncthreads();
+    if (B.n < kSmall) encode_block<true, false, true>(S, B, wave, lane, &a.result[b], nullptr);
+    else encode_block<false, false, true>(S, B, wave, lane, &a.result[b], nullptr);
+}
+
+hipError_t launch_encode_cdict(const BlockArgs &a, const void *cdict, hipStream_t s) {
+    if (a.nblocks <= 0) return hipSuccess;
+    hipLaunchKernelGGL(lz4_encode_cdict_kernel, dim3(a.nblocks), dim3(192), 0, s, a,
+                       (const uint8_t *)cdict);
+    return hipGetLastError();
 }
 
 hipError_t launch_encode(const BlockArgs &a, hipStream_t s) {

@@ -108,6 +108,57 @@ __device__ __forceinline__ uint32_t lane_val(uint32_t v, int l) {  // l wave-uni
     return (uint32_t)__builtin_amdgcn_readlane((int)v, l);
 }
 
+// ---- the encoder's hash table (lz4_encode.hip; lz4_cdict.hip prebuilds an image of it) ----
+// Table entries, the hash scaled onto [0, kHSize).  7328 entries make the block's LDS 17904
+// bytes, inside the 35 x 512-byte granules that fit 9 blocks = 27 waves per CU (7 per SIMD:
+// <= 72 VGPRs); the reference's 8192 entries fit 8 blocks, +4.6 % encode time for +0.6 % ratio
+// (measured; tools/enc_model.c models the ratio per table size).
+constexpr int kHSize = 7328;
+static_assert(kHSize < 8192 && kHSize % 8 == 0, "table size");
+// Bytes the table hash covers (the reference: 5, :456-473).  7 keeps short chance matches from
+// pre-empting longer ones: ratio up, 23 % fewer sequences (tools/enc_model.c key study,
+// DESIGN.md 3.1).
+constexpr int kKey = 7;
+
+// Hash of the kKey bytes at p (x0 = in[p..p+3], x1 = in[p+4..p+7]) onto [0, kHSize).  The
+// reference multiplies the 40-bit sequence by 889523592379 (:456-473), which needs
+// quarter-rate 32-bit multiplies here; any hash gives a valid stream, so this one uses
+// full-rate 24 x 24-bit multiplies (v_mul_u32_u24 / v_mad_u32_u24, which read only the low
+// 24 bits of their operands) of bytes 0-2, 3-5 and 6.
+__device__ __forceinline__ uint32_t hashk(uint32_t x0, uint32_t x1) {
+    static_assert(kKey == 7, "hashk covers bytes 0..6");
+    const uint32_t hi = __builtin_amdgcn_alignbyte(x1, x0, 3u);   // bytes 3..6 (the multiply takes 3..5)
+    // (__umul24 returns int: do the sums unsigned)
+    const uint32_t v = (uint32_t)__umul24(x0, 0x9E3779u) + (uint32_t)__umul24(hi, 0xC2B2AEu) +
+                       (uint32_t)__umul24((x1 >> 16) & 0xFFu, 0x27D4EBu);
+    return __umulhi(v, (uint32_t)kHSize);   // v scaled onto [0, kHSize): one v_mul_hi_u32
+}
+
+// ---- prepared dictionary (lz4_cdict.hip writes it, lz4_encode_kernel<.., EXT> reads it) ----
+// One device object, every region 16-byte aligned:
+//   [0, 16)                      header: magic, D (window bytes), maxSrcSize, 0
+//   [kCdTab, kCdTab + 2 kHSize)  the table prefix_history would build for window positions
+//                                [0, D) alone (u16 positions, 0 = empty)
+//   [kCdWin, kCdSize)            kCdFront bytes of pad, the window (the dictionary's last D
+//                                bytes, window position v at kCdWin + kCdFront + v), then pad to
+//                                the object's end (>= kCdBack bytes): a 16-byte load at any
+//                                window position, or up to 4 bytes before it, stays inside
+// D + maxSrcSize <= 65536 (one window of u16 positions), D a multiple of 64.
+constexpr uint32_t kCdMagic = 0x44435A4Cu;   // "LZCD"
+constexpr uint32_t kCdTab = 16u, kCdWin = kCdTab + 2u * (uint32_t)kHSize;
+constexpr uint32_t kCdFront = 16u, kCdBack = 256u;
+constexpr uint32_t kCdMaxWin = (uint32_t)kMaxBlock - 64u;   // maxSrcSize >= 1 leaves 65472
+constexpr uint32_t kCdSize = kCdWin + kCdFront + (uint32_t)kMaxBlock + kCdBack;
+static_assert(kCdWin % 16u == 0u && kCdSize % 16u == 0u, "prepared dictionary regions");
+struct CDictHdr {
+    uint32_t magic, D, max_src, zero;
+};
+// D of a prepared dictionary: min(dict_size, 65536 - max_src) rounded down to 64 (host and device)
+__host__ __device__ inline int cdict_window(int dict_size, int max_src) {
+    const int room = kMaxBlock - max_src;
+    return (dict_size < room ? dict_size : room) & ~63;
+}
+
 // ---- diagnostic phase timers (built only into libape_lz4_amd_stats.so) ----
 // Thread 0 of every workgroup accumulates s_memtime cycles per phase and adds them
 // to a per-kernel __device__ array at exit.  Never compiled into the product.
@@ -154,6 +205,12 @@ hipError_t launch_decode(const BlockArgs &a, bool partial, hipStream_t s);
 // workgroup per connection looping over its chunks in order (lz4_decode.hip)
 hipError_t launch_decode_chain(const BlockArgs &a, int nconn, int nq, hipStream_t s);
 hipError_t launch_encode(const BlockArgs &a, hipStream_t s);
+// against a prepared dictionary (layout above): the history is the object's window and table
+// image, not the bytes before each block (lz4_encode.hip, its EXT instantiation)
+hipError_t launch_encode_cdict(const BlockArgs &a, const void *cdict, hipStream_t s);
+// dict[dict_size - D, dict_size) -> the prepared dictionary at cdict (lz4_cdict.hip)
+hipError_t launch_cdict_prepare(const char *dict, int dict_size, int max_src, void *cdict,
+                                hipStream_t s);
 // the greedy-exact mode (lz4_encode_exact.hip): the reference's sequential parse, byte for byte
 hipError_t launch_encode_exact(const BlockArgs &a, hipStream_t s);
 // compress_destSize pass 2 (lz4_destsize.hip): scratch slot i (at scratch + i*stride, encoder

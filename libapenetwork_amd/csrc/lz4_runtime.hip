@@ -387,6 +387,45 @@ int APE_LZ4_compress_withPrefix_batch_dev(const char *const *d_src, const int *d
     return finish_launch(launch_encode(a, (hipStream_t)stream), "lz4_encode_kernel<prefix>");
 }
 
+// ---- prepared dictionaries (lz4_cdict.hip, the encoder's EXT instantiation) ----
+size_t APE_LZ4_cdict_size(void) { return (size_t)kCdSize; }
+
+int APE_LZ4_cdict_window(int dictSize, int maxSrcSize) {
+    if (dictSize < 0 || maxSrcSize < 1 || maxSrcSize > kMaxBlock) return -1;
+    const int D = cdict_window(dictSize, maxSrcSize);
+    return D < 64 ? 0 : D;
+}
+
+int APE_LZ4_cdict_prepare_dev(const char *d_dict, int dictSize, int maxSrcSize, void *d_cdict,
+                              size_t cdict_bytes, void *stream) {
+    if (dictSize < 0 || (dictSize > 0 && !d_dict) || maxSrcSize < 1 || maxSrcSize > kMaxBlock ||
+        !d_cdict || cdict_bytes < (size_t)kCdSize || ((uintptr_t)d_cdict & 15u)) {
+        snprintf(g_err, sizeof g_err, "cdict_prepare: dictSize %d, maxSrcSize %d (1..%d), object "
+                 "of %zu bytes at %p (need %u bytes, 16-byte aligned)", dictSize, maxSrcSize,
+                 kMaxBlock, cdict_bytes, d_cdict, kCdSize);
+        return APE_LZ4_GPU_EINVAL;
+    }
+    int rc = check_device();
+    if (rc) return rc;
+    return finish_launch(launch_cdict_prepare(d_dict, dictSize, maxSrcSize, d_cdict,
+                                              (hipStream_t)stream),
+                         "lz4_cdict_prepare_kernel");
+}
+
+int APE_LZ4_compress_usingCDict_batch_dev(const char *const *d_src, const int *d_srcSize,
+                                          char *const *d_dst, const int *d_dstCap, int *d_result,
+                                          int nblocks, const void *d_cdict, void *stream) {
+    if (nblocks < 0 || !d_cdict || ((uintptr_t)d_cdict & 15u) ||
+        (nblocks > 0 && (!d_src || !d_srcSize || !d_dst || !d_dstCap || !d_result)))
+        return APE_LZ4_GPU_EINVAL;
+    int rc = check_device();
+    if (rc) return rc;
+    return finish_launch(launch_encode_cdict(ptr_args(d_src, d_srcSize, d_dst, d_dstCap, nullptr,
+                                                      d_result, nblocks),
+                                             d_cdict, (hipStream_t)stream),
+                         "lz4_encode_cdict_kernel");
+}
+
 namespace {
 
 constexpr int kDsSub = 16384;   // destSize: blocks per scratch pass
