@@ -226,8 +226,9 @@ int APE_LZ4_compress_destSize_batch_scratch_dev(const char *const *d_src, int *d
  * only lengthens the run carried into the next slice; the block ends with one final literal
  * run.  Every other byte is the slices' own.
  *
- * Decoding such a block on the GPU is still one workgroup per block (the decoder has no
- * slice-parallel form). */
+ * Decoding such a block with APE_LZ4_decompress_safe_batch_dev is one workgroup per block.
+ * A block written with restart points and a seek index
+ * (APE_LZ4_compress_large_indexed_batch_dev, below) decodes one wave per segment. */
 int APE_LZ4_compress_large_slice_size(void);
 size_t APE_LZ4_compress_large_scratch_size(int nblocks, int maxSrcSize);
 int APE_LZ4_compress_large_batch_dev(const char *const *d_src, const int *d_srcSize,
@@ -242,6 +243,85 @@ int APE_LZ4_compress_large_timed_dev(const char *const *d_src, const int *d_srcS
                                      int nblocks, int maxSrcSize, int acceleration,
                                      void *d_scratch, size_t scratch_bytes, void *stream,
                                      float *ms4);
+
+/* ---- large blocks with restart points and a seek index (lz4_large.hip, lz4_decode.hip) ----
+ * A plain LZ4 block decodes serially: token positions are known only by walking it, and a
+ * match may copy bytes that are themselves copies.  Here the compressor cooperates.  With
+ * restartBytes = R > 0 (a positive multiple of the slice size S), every slice that starts at
+ * a multiple of R is encoded with NO history, and slice k at k*S otherwise with the bytes
+ * back to the last multiple of R (at most 65536 - len_k of them).  The block is still one
+ * ordinary LZ4 block (the stitch is unchanged: a literal run may merge across a restart
+ * point), but no match of the bytes [j R, (j + 1) R) reaches before j R, so the block falls
+ * into segments that decode independently once their positions are known.  The index says
+ * where they are.  restartBytes = 0 places no restart points: the block is byte-identical to
+ * APE_LZ4_compress_large_batch_dev's, which is this call with restartBytes 0 and no index.
+ *
+ * Index format: one per block at d_index + i * index_stride (16-byte aligned, the stride a
+ * multiple of 16), little-endian uint32 words
+ *     w[0] 0x3158494C ("LIX1")   w[1] nseg   w[2] n (decoded size)   w[3] c (block size)
+ *     w[4 + 2j], w[5 + 2j] = ip_j, op_j    for j = 0 .. nseg
+ * A valid index satisfies, and a decoder relies on nothing else:
+ *   - (ip_0, op_0) = (0, 0) and (ip_nseg, op_nseg) = (c, n); both columns are non-decreasing;
+ *   - for j < nseg, ip_j is the position of a token and op_j the output position at which
+ *     that sequence's literals start;
+ *   - every sequence that starts in [ip_j, ip_{j+1}) takes its match from output positions
+ *     >= op_j;
+ *   - segment nseg - 1 ends with the block's final literal run;
+ *   - a segment may be empty (ip_j == ip_{j+1}, then op_j == op_{j+1});
+ *   - when no block was produced (d_result[i] <= 0), w[1] = 0.
+ * The compressor writes nseg = ceil(n / R) segments for an input of n > 65536 and n > R bytes
+ * and one segment otherwise; entry j is the first sequence whose match lies at or after j R
+ * (op_j <= j R: its literals may begin before), so a stretch without any match gives empty
+ * segments and an incompressible input has its whole block in the last one.
+ *
+ * APE_LZ4_large_index_segments(maxSrcSize, restartBytes) = the most segments an input of up to
+ * maxSrcSize bytes gets (1 when maxSrcSize <= 65536 or restartBytes == 0);
+ * APE_LZ4_large_index_size = 16 + 8 (segments + 1) rounded up to 16, the least index_stride.
+ * Both are host-only and return 0 for arguments out of range (maxSrcSize outside
+ * [1, 0x7E000000], restartBytes negative or no multiple of S).
+ *
+ * APE_LZ4_compress_large_indexed_batch_dev: the arguments of APE_LZ4_compress_large_batch_dev
+ * with restartBytes, d_index, index_stride before the stream.  d_index == NULL places the
+ * restart points only.  APE_LZ4_GPU_EINVAL for a restartBytes that is neither 0 nor a positive
+ * multiple of S, a misaligned d_index, or a stride that is no multiple of 16 or below
+ * APE_LZ4_large_index_size(maxSrcSize, restartBytes).  Asynchronous, no allocation, no sync,
+ * graph-capturable; one more launch than the plain call when there is an index.
+ *
+ * APE_LZ4_decompress_safe_indexed_batch_dev: two stream-ordered launches, no scratch, no
+ * allocation, no sync, graph-capturable.  The index is never trusted.  The first launch
+ * judges each header: wrong magic, nseg == 0, w[3] != d_compressedSize[i],
+ * n > d_maxDecompressedSize[i] or a wrong first or last pair give d_result[i] = -1,
+ * nseg > maxSegments gives APE_LZ4_GPU_ERANGE, otherwise d_result[i] = n.  The second is
+ * nblocks x maxSegments waves (fewer than 2^31, index_stride >= 16 + 8 (maxSegments + 1),
+ * else APE_LZ4_GPU_EINVAL); wave (i, j) decodes src + ip_j into dst + op_j with the block's true
+ * end and capacity (the reference's end-of-block tests apply as in a serial decode), with
+ * op_j as the floor of every match, and for j < nseg - 1 up to the SEGMENT STOP: it
+ * succeeds when the parse reaches token position ip_{j+1} exactly with output position
+ * op_{j+1} exactly.  Stepping over the stop, reaching it at another output position or
+ * meeting the final sequence first fails; the last segment is an ordinary decode to the end,
+ * of n - op_j bytes.  A failing segment records -(p)-1, p counted from the block's start
+ * (index inconsistencies: p = ip_j); d_result[i] ends as the code with the smallest p,
+ * whatever the order the waves ran in.
+ *   - d_result[i] = r > 0: r and dst[0, r) are what APE_LZ4_decompress_safe gives.
+ *   - A negative result need not be the reference's code: a stream that a serial decoder
+ *     accepts but that breaks the index's invariants is rejected.  With nseg = 1 the call is
+ *     bit-exact with APE_LZ4_decompress_safe_batch_dev, codes included.
+ *   - Nothing outside src[0, c) and the index is read, nothing outside dst[0, cap) written.
+ * A block that is one literal run (incompressible input) is one segment: one wave. */
+int APE_LZ4_large_index_segments(int maxSrcSize, int restartBytes);
+size_t APE_LZ4_large_index_size(int maxSrcSize, int restartBytes);
+int APE_LZ4_compress_large_indexed_batch_dev(const char *const *d_src, const int *d_srcSize,
+                                             char *const *d_dst, const int *d_dstCap,
+                                             int *d_result, int nblocks, int maxSrcSize,
+                                             int acceleration, void *d_scratch,
+                                             size_t scratch_bytes, int restartBytes, void *d_index,
+                                             size_t index_stride, void *stream);
+int APE_LZ4_decompress_safe_indexed_batch_dev(const char *const *d_src,
+                                              const int *d_compressedSize, char *const *d_dst,
+                                              const int *d_maxDecompressedSize,
+                                              const void *d_index, size_t index_stride,
+                                              int maxSegments, int *d_result, int nblocks,
+                                              void *stream);
 
 /* One-shot routing: ape_lz4.h one-shot calls on blocks smaller than
  * `bytes` (compress: input size; decompress_safe/_partial: capacity) run the host codec,

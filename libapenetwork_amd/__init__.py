@@ -24,6 +24,8 @@ __all__ = [
     "socket_send_blocks", "socket_recv_blocks", "socket_stats", "set_oneshot_host_below",
     "Chain",
     "compress_large_slice_size", "compress_large_scratch_size", "compress_large_ptr_batch",
+    "large_index_segments", "large_index_size", "compress_large_indexed_ptr_batch",
+    "decompress_indexed_ptr_batch",
     "oneshot_on_gpu",
     "cdict_size", "cdict_window", "cdict_prepare", "compress_cdict_batch",
     "ONESHOT_HOST_ALL",
@@ -85,6 +87,10 @@ def lib():
             "APE_LZ4_compress_large_slice_size": (i, []),
             "APE_LZ4_compress_large_scratch_size": (sz, [i, i]),
             "APE_LZ4_compress_large_batch_dev": (i, [p, p, p, p, p, i, i, i, p, sz, p]),
+            "APE_LZ4_large_index_segments": (i, [i, i]),
+            "APE_LZ4_large_index_size": (sz, [i, i]),
+            "APE_LZ4_compress_large_indexed_batch_dev": (i, [p, p, p, p, p, i, i, i, p, sz, i, p, sz, p]),
+            "APE_LZ4_decompress_safe_indexed_batch_dev": (i, [p, p, p, p, p, sz, i, p, i, p]),
             "APE_LZ4_cdict_size": (sz, []),
             "APE_LZ4_cdict_window": (i, [i, i]),
             "APE_LZ4_cdict_prepare_dev": (i, [p, i, i, p, sz, p]),
@@ -434,6 +440,72 @@ def compress_large_ptr_batch(src_ptrs, src_sizes, dst_ptrs, caps, results, max_s
         max_src_size, acceleration, _ptr(scratch), scratch.numel(), _stream(stream)),
         "APE_LZ4_compress_large_batch_dev")
     return scratch
+
+
+def large_index_segments(max_src_size, restart_bytes):
+    """APE_LZ4_large_index_segments: the most segments an input of up to max_src_size bytes
+    gets with restart points every restart_bytes (0 for arguments out of range)."""
+    return lib().APE_LZ4_large_index_segments(max_src_size, restart_bytes)
+
+
+def large_index_size(max_src_size, restart_bytes):
+    """APE_LZ4_large_index_size: bytes of one block's seek index, the least index stride."""
+    return lib().APE_LZ4_large_index_size(max_src_size, restart_bytes)
+
+
+def _index_arg(what, index, n):
+    """The seek indexes of n blocks: a 2-D uint8 CUDA tensor [n, stride] (16-byte alignment
+    and the stride are checked by the C side)."""
+    _rows(index, what + " index", n)
+    return index.stride(0) if n > 1 else index.shape[1]
+
+
+def compress_large_indexed_ptr_batch(src_ptrs, src_sizes, dst_ptrs, caps, results, max_src_size,
+                                     restart_bytes, index=None, acceleration=1, scratch=None,
+                                     stream=None):
+    """compress_large_ptr_batch with a restart point every restart_bytes (0 or a multiple of the
+    slice size), and, when index (uint8 CUDA [N, stride >= large_index_size(max_src_size,
+    restart_bytes)]) is given, each block's seek index in its row.  Returns the scratch."""
+    import torch
+    _arr(src_sizes, "compress_large_indexed_ptr_batch src_sizes", torch.int32)
+    n = src_sizes.shape[0]
+    _ptr_args("compress_large_indexed_ptr_batch", n, src_ptrs=(src_ptrs, _i64()),
+              src_sizes=(src_sizes, _i32()), dst_ptrs=(dst_ptrs, _i64()), caps=(caps, _i32()),
+              results=(results, _i32()))
+    stride = 0
+    if index is not None:
+        stride = _index_arg("compress_large_indexed_ptr_batch", index, n)
+    if scratch is None:
+        need = compress_large_scratch_size(n, max_src_size)
+        if need == 0 or need >= 1 << 63:
+            raise ValueError("compress_large_indexed_ptr_batch: max_src_size outside "
+                             "[1, 0x7E000000] or too many slices for one call")
+        scratch = torch.empty(need, dtype=torch.uint8, device=src_sizes.device)
+    else:
+        _arr(scratch, "compress_large_indexed_ptr_batch scratch", torch.uint8)
+    _check(lib().APE_LZ4_compress_large_indexed_batch_dev(
+        _ptr(src_ptrs), _ptr(src_sizes), _ptr(dst_ptrs), _ptr(caps), _ptr(results), n,
+        max_src_size, acceleration, _ptr(scratch), scratch.numel(), restart_bytes, _ptr(index),
+        stride, _stream(stream)), "APE_LZ4_compress_large_indexed_batch_dev")
+    return scratch
+
+
+def decompress_indexed_ptr_batch(src_ptrs, comp_sizes, dst_ptrs, caps, index, max_segments,
+                                 results, stream=None):
+    """N x APE_LZ4_decompress_safe on blocks with a seek index (uint8 CUDA [N, stride], as
+    compress_large_indexed_ptr_batch wrote it), one wave per segment; a block with more than
+    max_segments segments gets ERANGE.  Pointer-array form."""
+    import torch
+    _arr(comp_sizes, "decompress_indexed_ptr_batch comp_sizes", torch.int32)
+    n = comp_sizes.shape[0]
+    _ptr_args("decompress_indexed_ptr_batch", n, src_ptrs=(src_ptrs, _i64()),
+              comp_sizes=(comp_sizes, _i32()), dst_ptrs=(dst_ptrs, _i64()), caps=(caps, _i32()),
+              results=(results, _i32()))
+    stride = _index_arg("decompress_indexed_ptr_batch", index, n)
+    _check(lib().APE_LZ4_decompress_safe_indexed_batch_dev(
+        _ptr(src_ptrs), _ptr(comp_sizes), _ptr(dst_ptrs), _ptr(caps), _ptr(index), stride,
+        max_segments, _ptr(results), n, _stream(stream)),
+        "APE_LZ4_decompress_safe_indexed_batch_dev")
 
 
 def cdict_size():

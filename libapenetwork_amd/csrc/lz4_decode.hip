@@ -34,6 +34,11 @@
 //         window start are copied by the whole wave.  The window is then flushed to
 //         dst with coalesced 16-byte stores.
 // Decoded blocks are not limited to 64 KiB: only the 64 KiB offset window is.
+//
+// A large block written with restart points and a seek index is decoded one wave per SEGMENT
+// (lz4_decode_indexed_kernel, at the end): the same code with a template flag STOP, under
+// which the parse ends at a given token position instead of the block's final run.  The four
+// instantiations without the flag compile to the device code they had before it existed.
 #include "lz4_gpu_internal.h"
 #include <type_traits>
 
@@ -192,10 +197,12 @@ struct Dec {
     int64_t oexit;
     int s0;          // staged window start
     int lane;
+    int stop;        // STOP: token position at which the segment ends (kNoStop: at the block's end)
     uint32_t mk[5];  // mk[k]: all ones on lanes with bit k set (chain_at's lifting selects, VGPRs)
 };
 
 enum { ST_MORE = 0, ST_DONE = 1, ST_ERR = 2 };
+constexpr int kNoStop = 0x7FFFFFFF;
 
 // Scalar restatement of one iteration of the reference loop (:1324-1458) for a
 // token at ip: appends its descriptor at desc[nd] (returns ST_MORE / ST_DONE) or
@@ -203,8 +210,10 @@ enum { ST_MORE = 0, ST_DONE = 1, ST_ERR = 2 };
 // FASTD: decompress_fast (endOnOutputSize, :1489): the block ends where the output
 // reaches cap exactly; no input-size tests (csize is only the readable bound of src);
 // the result is the input consumed.
-template <bool PARTIAL, bool FASTD = false>
+// STOP (a segment of an indexed block): a token at or past D.stop is not parsed.
+template <bool PARTIAL, bool FASTD = false, bool STOP = false>
 __device__ int parse_scalar(WaveLds &L, const Dec &D, int &ip, uint32_t &op, int &nd, int &res) {
+    if (STOP && ip >= D.stop) return ST_MORE;
     const uint32_t tok = sbyte(L, D.src, D.csize, D.s0, ip);
     ip++;
     int64_t lit = tok >> 4;
@@ -404,7 +413,9 @@ __device__ __forceinline__ void chain_at(const WaveLds &L, const Dec &D, int P, 
 // ST_MORE with P advanced (to the next token, or to a complex token when `cplx`), or
 // ST_DONE / ST_ERR with `res`.  Members are lanes [0, nm) in chain order: lane t re-reads
 // its sequence from the staged bytes.
-template <bool PARTIAL, bool DICT, bool FASTD = false>
+// STOP: the members end before the first one whose token lies at or past D.stop, and P
+// becomes that token's position (the caller compares it with the stop).
+template <bool PARTIAL, bool DICT, bool FASTD = false, bool STOP = false>
 __device__ int parse_window(WaveLds &L, const Dec &D, int &P, uint32_t &op, int &nd, int &res,
                             bool &cplx) {
     const int lane = D.lane;
@@ -450,12 +461,21 @@ __device__ int parse_window(WaveLds &L, const Dec &D, int &P, uint32_t &op, int 
     const uint32_t pB = bperm(posB, (t - (uint32_t)nmA) & 63u);
     const int nmAB = nmA + nmB;
     const int nm = nmAB + nmC;
-    const uint64_t M = (1ull << nm) - 1ull;   // nm <= 63
+    uint64_t M = (1ull << nm) - 1ull;   // nm <= 63
     const bool mem = (int)t < nm;
     uint32_t pos = (int)t < nmA ? posA : (uint32_t)(PB - P) + pB;   // relative to P
     if (nmC) {
         const uint32_t pC = bperm(posC, (t - (uint32_t)nmAB) & 63u);
         pos = (int)t < nmAB ? pos : (uint32_t)(PC - P) + pC;
+    }
+    int Pcut = -1;
+    if (STOP) {   // one more ballot: the members' token positions against the stop
+        const uint64_t cm = M & wave_ballot(P + (int)pos >= D.stop);
+        if (cm) {
+            const int T = __ffsll((long long)cm) - 1;
+            Pcut = P + (int)lane_val(pos, T);
+            M = (1ull << T) - 1ull;
+        }
     }
 
     // member t = the sequence at P + pos, re-read from the staged bytes
@@ -535,6 +555,10 @@ __device__ int parse_window(WaveLds &L, const Dec &D, int &P, uint32_t &op, int 
         }
     }
     if (st == ST_MORE) P = Pn;
+    if (STOP && st == ST_MORE && Pcut >= 0) {
+        P = Pcut;
+        cplx = false;
+    }
     return st;
 }
 
@@ -944,34 +968,55 @@ __device__ __forceinline__ void copy_batch(WaveLds &L, const Dec &D, Win &W, int
 
 }  // namespace
 
-// One block (block index b of the batch) decoded by the calling wave.
-template <bool PARTIAL, bool DICT, bool FASTD>
+// One segment of an indexed block (lz4_decode_indexed_kernel): the bytes from the segment's
+// first token to the block's end, the output room from its first byte to the block's
+// capacity, and the token position (from src) at which the segment ends.
+struct Seg {
+    gcu8 *src;
+    gu8 *dst;
+    int csize, cap, stop;
+    int res;    // out: the result (wave-uniform)
+    bool hit;   // out: the parse ended at `stop` (the result is then the output produced)
+};
+
+// One block (block index b of the batch) decoded by the calling wave.  STOP: the block is
+// the segment *sg instead (a, b unused), and the result goes to sg->res, not to a.result.
+template <bool PARTIAL, bool DICT, bool FASTD, bool STOP = false>
 __device__ __forceinline__ void decode_block(WaveLds &L, const BlockArgs &a, const int b,
-                                             const int lane) {
+                                             const int lane, Seg *sg = nullptr) {
     Dec D;
-    D.dst = (gu8 *)(a.dst ? a.dst[b] : a.dst_base + (size_t)b * a.dst_stride);
-    if (a.frame_off) {   // framed stream: [le32 size][block] (lz4_frame.hip)
-        // The header is untrusted: it must fit the frame the offsets give (ref
-        // src/ape_socket.c:1382-1384 rejects a size above the data it has).  A frame
-        // shorter than its header, or a size < 0 or past the next frame, is malformed:
-        // -1, nothing read beyond the frame, nothing written.
-        const long long f0 = a.frame_off[b], avail = a.frame_off[b + 1] - f0 - 4;
-        int hdr = -1;
-        gcu8 *f = (gcu8 *)(a.src_base + f0);
-        if (avail >= 0)
-            hdr = (int)((uint32_t)f[0] | ((uint32_t)f[1] << 8) | ((uint32_t)f[2] << 16) |
-                        ((uint32_t)f[3] << 24));
-        if (hdr < 0 || (long long)hdr > avail) {
-            if (lane == 0) a.result[b] = -1;
-            return;
-        }
-        D.csize = hdr;
-        D.src = f + 4;
+    if (STOP) {
+        D.src = sg->src;
+        D.dst = sg->dst;
+        D.csize = sg->csize;
+        D.cap = sg->cap;
+        D.stop = sg->stop;
+        sg->hit = false;
     } else {
-        D.src = (gcu8 *)(a.src ? a.src[b] : a.src_base + (size_t)b * a.src_stride);
-        D.csize = a.src_size[b];
+        D.dst = (gu8 *)(a.dst ? a.dst[b] : a.dst_base + (size_t)b * a.dst_stride);
+        if (a.frame_off) {   // framed stream: [le32 size][block] (lz4_frame.hip)
+            // The header is untrusted: it must fit the frame the offsets give (ref
+            // src/ape_socket.c:1382-1384 rejects a size above the data it has).  A frame
+            // shorter than its header, or a size < 0 or past the next frame, is malformed:
+            // -1, nothing read beyond the frame, nothing written.
+            const long long f0 = a.frame_off[b], avail = a.frame_off[b + 1] - f0 - 4;
+            int hdr = -1;
+            gcu8 *f = (gcu8 *)(a.src_base + f0);
+            if (avail >= 0)
+                hdr = (int)((uint32_t)f[0] | ((uint32_t)f[1] << 8) | ((uint32_t)f[2] << 16) |
+                            ((uint32_t)f[3] << 24));
+            if (hdr < 0 || (long long)hdr > avail) {
+                if (lane == 0) a.result[b] = -1;
+                return;
+            }
+            D.csize = hdr;
+            D.src = f + 4;
+        } else {
+            D.src = (gcu8 *)(a.src ? a.src[b] : a.src_base + (size_t)b * a.src_stride);
+            D.csize = a.src_size[b];
+        }
+        D.cap = a.dst_cap ? a.dst_cap[b] : (int)a.dst_stride;
     }
-    D.cap = a.dst_cap ? a.dst_cap[b] : (int)a.dst_stride;
     D.oexit = PARTIAL ? a.target[b] : 0;
     if (PARTIAL && D.oexit > (int64_t)D.cap - kMFLimit) D.oexit = (int64_t)D.cap - kMFLimit;
     D.lane = lane;
@@ -995,11 +1040,12 @@ __device__ __forceinline__ void decode_block(WaveLds &L, const BlockArgs &a, con
         return;
     }
     if (D.cap == 0 || D.csize <= 0) {
-        if (lane == 0) {
+        if (STOP || lane == 0) {
             int r;
             if (D.cap == 0) r = (D.csize == 1 && D.src[0] == 0) ? 0 : -1;
             else r = ((D.src ? D.src[0] : 0u) >= 0xF0) ? -3 : -2;
-            a.result[b] = r;
+            if (STOP) sg->res = r;
+            else a.result[b] = r;
         }
         return;
     }
@@ -1009,7 +1055,9 @@ __device__ __forceinline__ void decode_block(WaveLds &L, const BlockArgs &a, con
     // literals branch (:1346-1366): ret = the run if it ends exactly at csize and fits cap,
     // else -(ip)-1.  Here the length bytes are scanned 64 at a time and the run is copied
     // global -> global, 16 bytes per lane, without the LDS staging or the output window.
-    if (!PARTIAL && !FASTD && !DICT && D.csize >= 32 && D.cap > 0 && D.src[0] >= 0xF0u) {
+    // (a segment that ends at a stop is no final run)
+    if (!PARTIAL && !FASTD && !DICT && D.csize >= 32 && D.cap > 0 && D.src[0] >= 0xF0u &&
+        (!STOP || D.stop == kNoStop)) {
         // bytes 1.. while 255 and ip < csize - 15 after the read (:1334-1337): J = the last
         // one read; all before it are 255
         int J = 0;
@@ -1026,7 +1074,8 @@ __device__ __forceinline__ void decode_block(WaveLds &L, const BlockArgs &a, con
         const long long L = 15ll + 255ll * (J - 1) + (long long)D.src[J];
         if ((long long)J + 1 + L == (long long)D.csize) {
             if (L > (long long)D.cap) {
-                if (lane == 0) a.result[b] = -(J + 1) - 1;
+                if (STOP) sg->res = -(J + 1) - 1;
+                else if (lane == 0) a.result[b] = -(J + 1) - 1;
                 return;
             }
             gcu8 *s = D.src + J + 1;
@@ -1043,7 +1092,8 @@ __device__ __forceinline__ void decode_block(WaveLds &L, const BlockArgs &a, con
             }
             for (; k < n16; k += 64) gstore16(d + 16 * k, gload16(s + 16 * k));
             for (int i = 16 * n16 + lane; i < (int)L; i += 64) d[i] = s[i];
-            if (lane == 0) a.result[b] = (int)L;
+            if (STOP) sg->res = (int)L;
+            else if (lane == 0) a.result[b] = (int)L;
             return;
         }
     }
@@ -1068,7 +1118,8 @@ __device__ __forceinline__ void decode_block(WaveLds &L, const BlockArgs &a, con
         int ip = 0, nd = 0;
         uint32_t op0 = 0;
         (void)parse_scalar<PARTIAL, FASTD>(L, D, ip, op0, nd, result);
-        if (lane == 0) a.result[b] = result;
+        if (STOP) sg->res = result;
+        else if (lane == 0) a.result[b] = result;
         return;
     }
 
@@ -1088,10 +1139,24 @@ __device__ __forceinline__ void decode_block(WaveLds &L, const BlockArgs &a, con
         // s_cselect of 64-bit masks per pass); a complex token may jump far past the staged
         // bytes, which the loop condition then sees.  (restage may now also hold with nd >= 64:
         // every descriptor is copied before the restage, as at any restage)
-        while (st == ST_MORE && nd < kBatch && P - D.s0 + kWinNeed <= kStage) {
+        while (st == ST_MORE && nd < kBatch && P - D.s0 + kWinNeed <= kStage &&
+               (!STOP || P < D.stop)) {
             bool cplx;
-            st = parse_window<PARTIAL, DICT, FASTD>(L, D, P, op, nd, result, cplx);
-            if (st == ST_MORE && cplx) st = parse_scalar<PARTIAL, FASTD>(L, D, P, op, nd, result);
+            st = parse_window<PARTIAL, DICT, FASTD, STOP>(L, D, P, op, nd, result, cplx);
+            if (st == ST_MORE && cplx)
+                st = parse_scalar<PARTIAL, FASTD, STOP>(L, D, P, op, nd, result);
+        }
+        if (STOP && st == ST_MORE && P >= D.stop) {
+            // the segment stop: reached exactly, the segment is what was parsed so far (all
+            // of it is copied below, as at a block's end); a chain that stepped over it fails
+            if (P == D.stop) {
+                st = ST_DONE;
+                result = (int)op;
+                sg->hit = true;
+            } else {
+                st = ST_ERR;
+                result = -1;
+            }
         }
         const bool restage = st == ST_MORE && P - D.s0 + kWinNeed > kStage;
         STAT(0);
@@ -1128,7 +1193,8 @@ __device__ __forceinline__ void decode_block(WaveLds &L, const BlockArgs &a, con
             STAT_ADD(4, 1);
         }
     }
-    if (lane == 0) a.result[b] = result;
+    if (STOP) sg->res = result;
+    else if (lane == 0) a.result[b] = result;
     STAT_ADD(10, 1);
 #ifdef APE_LZ4_STATS
     STAT_ADD(7, sub_[0]);    // slides
@@ -1163,6 +1229,89 @@ lz4_decode_chain_kernel(BlockArgs a, int nconn, int nq) {
     }
 }
 
+
+// ---- indexed blocks (include/ape_lz4_gpu.h, "large blocks with restart points and a seek
+// index") ----
+// The index is untrusted.  Its header is judged by one function, used by the check launch
+// (which sets d_result[i]) and again by every wave of the decode launch, so what a wave does
+// never depends on what another wave has recorded: 0 = usable, else the block's result.
+__device__ __forceinline__ int index_header(const uint32_t *w, int csize, int cap, int max_seg) {
+    const uint32_t nseg = w[1], n = w[2], c = w[3];
+    if (w[0] != kIxMagic || nseg == 0u || c != (uint32_t)csize) return -1;
+    if ((int64_t)n > (int64_t)cap) return -1;
+    if (nseg > 1u && csize <= 0) return -1;
+    // (the stride holds max_seg + 1 pairs: nothing past the index is read)
+    if (nseg > (uint32_t)max_seg) return kErange;
+    const size_t e = 4 + 2 * (size_t)nseg;
+    if (w[4] != 0u || w[5] != 0u || w[e] != c || w[e + 1] != n) return -1;
+    return 0;
+}
+
+__global__ void __launch_bounds__(256)
+lz4_index_check_kernel(IndexedArgs a) {
+    const int i = (int)(blockIdx.x * 256u + threadIdx.x);
+    if (i >= a.nblocks) return;
+    const uint32_t *w = (const uint32_t *)(a.index + (size_t)i * a.index_stride);
+    const int e = index_header(w, a.src_size[i], a.dst_cap[i], a.max_seg);
+    a.result[i] = e ? e : (int)w[2];
+}
+
+// Wave (i, j) decodes segment j of block i: src + ip_j into dst + op_j, against the block's
+// true end and capacity, matches no further back than op_j, up to the token at ip_{j+1}.  A
+// failing segment records -(p)-1, p counted from the block's start, by an atomic max on the
+// unsigned view of d_result[i]: every negative code beats the size the check launch wrote,
+// and the smallest p beats the others, whichever wave comes first.
+__global__ void __launch_bounds__(64)
+lz4_decode_indexed_kernel(IndexedArgs a) {
+    __shared__ WaveLds L;
+    const int i = (int)(blockIdx.x / (uint32_t)a.max_seg), lane = (int)threadIdx.x;
+    const uint32_t j = blockIdx.x % (uint32_t)a.max_seg;
+    const uint32_t *w = (const uint32_t *)(a.index + (size_t)i * a.index_stride);
+    const int csize = a.src_size[i], cap = a.dst_cap[i];
+    if (index_header(w, csize, cap, a.max_seg)) return;
+    const uint32_t nseg = w[1], n = w[2];
+    if (j >= nseg) return;
+    const uint32_t *pr = w + 4 + 2 * (size_t)j;
+    const uint32_t ip0 = pr[0], op0 = pr[1], ip1 = pr[2], op1 = pr[3];
+    const bool lastseg = j + 1u == nseg;
+    uint32_t p = ip0;   // where a failure is reported (the segment's start unless the parse says)
+    bool ok = true;
+    if (nseg > 1u) {   // (one segment: both pairs are the header's, checked above)
+        ok = ip0 <= ip1 && op0 <= op1 && ip1 <= (uint32_t)csize && op1 <= n &&
+             (lastseg ? ip0 < ip1 : (ip0 < ip1 || op0 == op1));
+        if (ok && ip0 == ip1) return;   // an empty segment
+    }
+    if (ok) {
+        Seg sg;
+        sg.src = (gcu8 *)a.src[i] + ip0;
+        sg.dst = (gu8 *)a.dst[i] + op0;
+        sg.csize = csize - (int)ip0;
+        sg.cap = cap - (int)op0;
+        sg.stop = lastseg ? kNoStop : (int)(ip1 - ip0);
+        const BlockArgs none{};
+        decode_block<false, false, false, true>(L, none, 0, lane, &sg);
+        const int r = sg.res;
+        if (r < 0) {
+            ok = false;
+            p = ip0 + (uint32_t)(-(r + 1));
+        } else {
+            ok = sg.hit == !lastseg && (uint32_t)r == op1 - op0;
+        }
+    }
+    if (!ok && lane == 0)
+        atomicMax((unsigned int *)&a.result[i], ~umin(p, 0x7FFFFFFEu));   // -(p)-1
+}
+
+hipError_t launch_decode_indexed(const IndexedArgs &a, hipStream_t s) {
+    if (a.nblocks <= 0) return hipSuccess;
+    hipLaunchKernelGGL(lz4_index_check_kernel, dim3(((unsigned)a.nblocks + 255u) / 256u), dim3(256),
+                       0, s, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(lz4_decode_indexed_kernel, dim3((unsigned)a.nblocks * (unsigned)a.max_seg),
+                       dim3(64), 0, s, a);
+    return hipGetLastError();
+}
 
 hipError_t launch_decode_chain(const BlockArgs &a, int nconn, int nq, hipStream_t s) {
     if (nconn <= 0 || nq <= 0) return hipSuccess;

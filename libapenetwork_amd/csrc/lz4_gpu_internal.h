@@ -240,8 +240,35 @@ struct LargeArgs {
     uint32_t *s_off, *s_carry, *s_lead, *s_next;       // offsets kernel -> stitch kernel
     uint32_t *run_pos, *run_anchor;                    // per input, nsl + 1 entries
     char *buf;                // slot buffers (the scratch base before large_scratch_layout)
+    int restart;              // R: every R bytes a slice starts without history (0 = never)
+    char *index;              // seek index per input at index + i * index_stride (nullable)
+    size_t index_stride;
 };
 int large_slice_size();
+// Seek index of an indexed block (layout in include/ape_lz4_gpu.h): little-endian uint32 words
+// {magic, nseg, n, c}, then nseg + 1 pairs (ip_j, op_j).
+constexpr uint32_t kIxMagic = 0x3158494Cu;   // "LIX1"
+// segments of an input of up to max_src bytes with restart points every `restart` bytes
+inline long long large_index_segments(int max_src, int restart) {
+    if (max_src <= kMaxBlock || restart <= 0) return 1;
+    return ((long long)max_src + restart - 1) / restart;
+}
+inline size_t large_index_size(int max_src, int restart) {
+    return ((size_t)(16 + 8 * (large_index_segments(max_src, restart) + 1)) + 15) & ~(size_t)15;
+}
+struct IndexedArgs {
+    const char *const *src;   // caller's arrays, one entry per block
+    const int *src_size;
+    char *const *dst;
+    const int *dst_cap;
+    const char *index;        // block i's index at index + i * index_stride
+    size_t index_stride;
+    int max_seg;              // waves per block; a block with more segments gets kErange
+    int *result;
+    int nblocks;
+};
+// check launch + one wave per (block, segment) (lz4_decode.hip)
+hipError_t launch_decode_indexed(const IndexedArgs &a, hipStream_t s);
 size_t large_scratch_layout(int nblocks, int max_src, LargeArgs *out);
 hipError_t launch_large(const LargeArgs &a, int accel, hipStream_t s, hipEvent_t *ev = nullptr);
 hipError_t launch_synth(char *out, size_t stride, int n, long long first, int nblocks,

@@ -17,6 +17,10 @@
 //   4. large_stitch_kernel   one workgroup per slice: merged token + length bytes, the
 //                            slice's own literals from the source, the rest of its
 //                            sequences from scratch
+// With restart points (LargeArgs::restart = R > 0) the plan gives a slice only the history back
+// to the last multiple of R, so no match of [j R, (j + 1) R) reaches before j R; a fifth launch,
+// large_index_kernel, then writes each input's seek index from what the offsets kernel left
+// (APE_LZ4_compress_large_indexed_batch_dev; the decoder of such blocks is in lz4_decode.hip).
 // Work per stitch workgroup is O(S): a slice copies its OWN trailing literals to their place
 // in the run they belong to (the run's position comes from the next slice with a body), so
 // an incompressible input of any size never gathers onto one workgroup.
@@ -61,7 +65,9 @@ large_plan_kernel(LargeArgs a) {
             const uint32_t start = k * kS;
             src += start;
             size = (int)umin(kS, (uint32_t)n - start);
-            prefix = (int)start;
+            // history back to the last restart point at or before the slice (a slice AT one
+            // is encoded with none: no match of its group reaches before the group's start)
+            prefix = (int)(a.restart > 0 ? start % (uint32_t)a.restart : start);
             cap = (int)a.stride;   // >= compressBound(S): every slice fits
         }
     }
@@ -165,6 +171,56 @@ large_offsets_kernel(LargeArgs a) {
         const uint32_t e = umax(ce, wave_shr1(incl, 0u));
         if (live) a.s_next[t] = kNoBodyEnc - e;
         ce = umax(ce, lane_val(incl, 63));
+    }
+}
+
+// The seek index of every input (a.index != nullptr), one wave per input, after the offsets
+// kernel.  Group j = the slices of [j R, (j + 1) R).  Entry j is the token position and the
+// run anchor of the first slice at or after slice j R / S that has a body (its piece starts
+// with the sequence whose literals begin at the anchor, and the anchor is at or before the
+// group's start: no earlier slice of the group has a match); without such a slice it is the
+// final run's.  A group without any body therefore becomes an empty segment.
+__global__ void __launch_bounds__(64)
+large_index_kernel(LargeArgs a) {
+    const int i = blockIdx.x;
+    const int lane = lane_id();
+    uint32_t *w = (uint32_t *)(a.index + (size_t)i * a.index_stride);
+    const int n = a.src_size[i], r = a.result[i];
+    const bool one = n <= kMaxBlock || a.restart <= 0 || n <= a.restart;
+    if (r <= 0 || one) {   // no block: nseg = 0; one segment: the whole block
+        if (lane == 0) {
+            w[0] = kIxMagic;
+            w[1] = r > 0 ? 1u : 0u;
+            w[2] = r > 0 ? (uint32_t)n : 0u;
+            w[3] = r > 0 ? (uint32_t)r : 0u;
+            if (r > 0) {
+                w[4] = 0u;
+                w[5] = 0u;
+                w[6] = (uint32_t)r;
+                w[7] = (uint32_t)n;
+            }
+        }
+        return;
+    }
+    const uint32_t un = (uint32_t)n, R = (uint32_t)a.restart;
+    const uint32_t K = (un + kS - 1u) / kS, nseg = (un + R - 1u) / R, per = R / kS;
+    const size_t t0 = (size_t)i * a.nsl;
+    const uint32_t *runR = a.run_pos + (size_t)i * (a.nsl + 1), *runA = a.run_anchor + (size_t)i * (a.nsl + 1);
+    const uint32_t fin = un - runA[K], ftok = runR[K] - (1u + ext_len(fin));   // the final run's token
+    if (lane == 0) {
+        w[0] = kIxMagic;
+        w[1] = nseg;
+        w[2] = un;
+        w[3] = (uint32_t)r;
+        w[4 + 2 * nseg] = (uint32_t)r;
+        w[5 + 2 * nseg] = un;
+    }
+    for (uint32_t j = (uint32_t)lane; j < nseg; j += 64u) {
+        const uint32_t g = j * per;   // < K
+        const uint32_t len = umin(kS, un - g * kS);
+        const uint32_t m = (uint32_t)a.s_tail[t0 + g] < len ? g : a.s_next[t0 + g];
+        w[4 + 2 * j] = m < K ? a.s_off[t0 + m] : ftok;
+        w[5 + 2 * j] = runA[m];
     }
 }
 
@@ -313,6 +369,10 @@ hipError_t launch_large(const LargeArgs &a, int accel, hipStream_t s, hipEvent_t
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = mark(4);
+    if (e == hipSuccess && a.index) {
+        hipLaunchKernelGGL(large_index_kernel, dim3(a.nblocks), dim3(64), 0, s, a);
+        e = hipGetLastError();
+    }
     return e;
 }
 

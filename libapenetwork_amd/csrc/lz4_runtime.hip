@@ -530,7 +530,71 @@ size_t APE_LZ4_compress_large_scratch_size(int nblocks, int maxSrcSize) {
 namespace {
 int large_batch(const char *const *d_src, const int *d_srcSize, char *const *d_dst,
                 const int *d_dstCap, int *d_result, int nblocks, int maxSrcSize, int acceleration,
-                void *d_scratch, size_t scratch_bytes, void *stream, hipEvent_t *ev);
+                void *d_scratch, size_t scratch_bytes, void *stream, hipEvent_t *ev,
+                int restartBytes = 0, void *d_index = nullptr, size_t index_stride = 0);
+// restartBytes: 0 or a positive multiple of the slice size
+bool restart_ok(int restartBytes) {
+    return restartBytes >= 0 && restartBytes % large_slice_size() == 0;
+}
+}
+
+int APE_LZ4_large_index_segments(int maxSrcSize, int restartBytes) {
+    if (maxSrcSize < 1 || maxSrcSize > kLargeMaxSrc || !restart_ok(restartBytes)) return 0;
+    return (int)large_index_segments(maxSrcSize, restartBytes);
+}
+
+size_t APE_LZ4_large_index_size(int maxSrcSize, int restartBytes) {
+    if (maxSrcSize < 1 || maxSrcSize > kLargeMaxSrc || !restart_ok(restartBytes)) return 0;
+    return large_index_size(maxSrcSize, restartBytes);
+}
+
+int APE_LZ4_compress_large_indexed_batch_dev(const char *const *d_src, const int *d_srcSize,
+                                             char *const *d_dst, const int *d_dstCap,
+                                             int *d_result, int nblocks, int maxSrcSize,
+                                             int acceleration, void *d_scratch,
+                                             size_t scratch_bytes, int restartBytes, void *d_index,
+                                             size_t index_stride, void *stream) {
+    return large_batch(d_src, d_srcSize, d_dst, d_dstCap, d_result, nblocks, maxSrcSize,
+                       acceleration, d_scratch, scratch_bytes, stream, nullptr, restartBytes,
+                       d_index, index_stride);
+}
+
+int APE_LZ4_decompress_safe_indexed_batch_dev(const char *const *d_src,
+                                              const int *d_compressedSize, char *const *d_dst,
+                                              const int *d_maxDecompressedSize,
+                                              const void *d_index, size_t index_stride,
+                                              int maxSegments, int *d_result, int nblocks,
+                                              void *stream) {
+    if (nblocks < 0 || (nblocks > 0 && (!d_src || !d_compressedSize || !d_dst ||
+                                         !d_maxDecompressedSize || !d_index || !d_result))) {
+        snprintf(g_err, sizeof g_err, "invalid argument");
+        return APE_LZ4_GPU_EINVAL;
+    }
+    // one wave per (block, segment) in a one-dimensional grid; the stride holds the header
+    // and maxSegments + 1 pairs, so a block's index is never read past
+    if (maxSegments < 1 || (long long)nblocks * maxSegments > 0x7FFFFFFFll ||
+        ((uintptr_t)d_index & 15u) || index_stride % 16u ||
+        index_stride < 16u + 8u * ((size_t)maxSegments + 1u)) {
+        snprintf(g_err, sizeof g_err, "decompress_safe_indexed: maxSegments %d x %d blocks, index "
+                 "at %p with stride %zu (need 16-byte alignment, a stride that is a multiple of "
+                 "16 and >= 16 + 8 (maxSegments + 1), and fewer than 2^31 segments in all)",
+                 maxSegments, nblocks, d_index, index_stride);
+        return APE_LZ4_GPU_EINVAL;
+    }
+    int rc = check_device();
+    if (rc) return rc;
+    IndexedArgs a{};
+    a.src = d_src;
+    a.src_size = d_compressedSize;
+    a.dst = d_dst;
+    a.dst_cap = d_maxDecompressedSize;
+    a.index = (const char *)d_index;
+    a.index_stride = index_stride;
+    a.max_seg = maxSegments;
+    a.result = d_result;
+    a.nblocks = nblocks;
+    return finish_launch(launch_decode_indexed(a, (hipStream_t)stream),
+                         "lz4_index_check_kernel + lz4_decode_indexed_kernel");
 }
 
 int APE_LZ4_compress_large_batch_dev(const char *const *d_src, const int *d_srcSize,
@@ -568,7 +632,8 @@ int APE_LZ4_compress_large_timed_dev(const char *const *d_src, const int *d_srcS
 namespace {
 int large_batch(const char *const *d_src, const int *d_srcSize, char *const *d_dst,
                 const int *d_dstCap, int *d_result, int nblocks, int maxSrcSize, int acceleration,
-                void *d_scratch, size_t scratch_bytes, void *stream, hipEvent_t *ev) {
+                void *d_scratch, size_t scratch_bytes, void *stream, hipEvent_t *ev,
+                int restartBytes, void *d_index, size_t index_stride) {
     if (nblocks < 0 || (nblocks > 0 && (!d_src || !d_srcSize || !d_dst || !d_dstCap ||
                                          !d_result || !d_scratch))) {
         snprintf(g_err, sizeof g_err, "invalid argument");
@@ -579,10 +644,25 @@ int large_batch(const char *const *d_src, const int *d_srcSize, char *const *d_d
                  kLargeMaxSrc);
         return APE_LZ4_GPU_EINVAL;
     }
+    if (!restart_ok(restartBytes)) {
+        snprintf(g_err, sizeof g_err, "compress_large: restartBytes %d is neither 0 nor a positive "
+                 "multiple of the slice size %d", restartBytes, large_slice_size());
+        return APE_LZ4_GPU_EINVAL;
+    }
+    if (d_index && (((uintptr_t)d_index & 15u) || index_stride % 16u ||
+                    index_stride < large_index_size(maxSrcSize, restartBytes))) {
+        snprintf(g_err, sizeof g_err, "compress_large: index at %p with stride %zu, need 16-byte "
+                 "alignment and a stride that is a multiple of 16 and >= %zu", d_index,
+                 index_stride, large_index_size(maxSrcSize, restartBytes));
+        return APE_LZ4_GPU_EINVAL;
+    }
     int rc = check_device();
     if (rc) return rc;
     if (nblocks == 0) return APE_LZ4_GPU_OK;
     LargeArgs a{};
+    a.restart = restartBytes;
+    a.index = (char *)d_index;
+    a.index_stride = index_stride;
     a.src = d_src;
     a.src_size = d_srcSize;
     a.dst = d_dst;

@@ -12,9 +12,19 @@ slice tools/ratio_files.py uses ("sobin").  Per case:
   host         one input through the one-shot host codec (what a caller gets today)
   ref_ratio    the reference's compress_default ratio on one input (oracle/_ref, when built)
 
+--decode runs the way back instead (profiles/large_indexed.json): per case and restart period
+R in {128 KiB, 256 KiB, 1 MiB}, compress_large_indexed, then
+
+  ratio_vs_R0  the block's size with R = 0 over its size with R (what the restart points cost)
+  indexed      decompress_indexed_ptr_batch, one wave per segment
+  plain        decompress_ptr_batch on the same blocks, one wave per block
+
+both decoders warmed up, then timed alternately (HIP events, median of --reps each); the
+output of each is compared with the source.
+
 Each case runs in a child process of its own under a time limit; the first failure ends the
 run.  Prints one JSON line per case and writes profiles/large_compress.json (--out).
-usage: large_bench.py [--reps 5] [--out profiles/large_compress.json] [--case NAME]"""
+usage: large_bench.py [--decode] [--reps 5] [--out FILE] [--case NAME]"""
 import argparse
 import ctypes as C
 import glob
@@ -63,17 +73,7 @@ def run_case(name, reps):
     total = nin * n
     S = amd.compress_large_slice_size()
     flat = torch.empty(total, dtype=torch.uint8, device="cuda")
-    if kind == "appC":
-        amd.synth_blocks(flat.view(-1, 65536), 65536, 0, 1)
-    elif kind == "pysrc":   # ratio_files.py's other corpus: 4 MiB of Python sources, repeated
-        py = b"".join(open(f, "rb").read() for f in sorted(glob.glob("/usr/lib/python3.10/*.py")))
-        assert len(py) >= n, "Python sources shorter than 4 MiB"
-        flat.view(-1, n)[:] = torch.from_numpy(np.frombuffer(py[:n], dtype=np.uint8).copy()).cuda()
-    else:   # one 16 MiB slice of the file, repeated
-        one = torch.from_numpy(np.frombuffer(sobin(16 * MB), dtype=np.uint8).copy()).cuda()
-        assert one.numel() == 16 * MB, "torch/lib slice shorter than 16 MiB"
-        flat.view(-1, 16 * MB)[:] = one
-    torch.cuda.synchronize()
+    fill(torch, np, kind, flat, n)
     i32 = lambda xs: torch.tensor(xs, dtype=torch.int32, device="cuda")
     i64 = lambda xs: torch.tensor(xs, dtype=torch.int64, device="cuda")
     bound = amd.compressBound(n)
@@ -153,21 +153,110 @@ def run_case(name, reps):
     return rec
 
 
+def fill(torch, np, kind, flat, n):
+    """The case's inputs, laid end to end in flat."""
+    import libapenetwork_amd as amd
+    if kind == "appC":
+        amd.synth_blocks(flat.view(-1, 65536), 65536, 0, 1)
+    elif kind == "pysrc":   # ratio_files.py's other corpus: 4 MiB of Python sources, repeated
+        py = b"".join(open(f, "rb").read() for f in sorted(glob.glob("/usr/lib/python3.10/*.py")))
+        assert len(py) >= n, "Python sources shorter than 4 MiB"
+        flat.view(-1, n)[:] = torch.from_numpy(np.frombuffer(py[:n], dtype=np.uint8).copy()).cuda()
+    else:
+        one = torch.from_numpy(np.frombuffer(sobin(16 * MB), dtype=np.uint8).copy()).cuda()
+        assert one.numel() == 16 * MB, "torch/lib slice shorter than 16 MiB"
+        flat.view(-1, 16 * MB)[:] = one
+    torch.cuda.synchronize()
+
+
+DECODE_R = (128 << 10, 256 << 10, MB)
+
+
+def run_decode_case(name, reps):
+    import numpy as np
+    import torch
+    import libapenetwork_amd as amd
+    kind, nin, n = CASES[name]
+    total = nin * n
+    flat = torch.empty(total, dtype=torch.uint8, device="cuda")
+    fill(torch, np, kind, flat, n)
+    i32 = lambda xs: torch.tensor(xs, dtype=torch.int32, device="cuda")
+    i64 = lambda xs: torch.tensor(xs, dtype=torch.int64, device="cuda")
+    bound = amd.compressBound(n)
+    slot = (bound + 15) // 16 * 16
+    out = torch.empty(nin * slot, dtype=torch.uint8, device="cuda")
+    back = torch.empty(total, dtype=torch.uint8, device="cuda")
+    sptr = i64([flat.data_ptr() + i * n for i in range(nin)])
+    dptr = i64([out.data_ptr() + i * slot for i in range(nin)])
+    bptr = i64([back.data_ptr() + i * n for i in range(nin)])
+    sizes, caps, res, dres = i32([n] * nin), i32([bound] * nin), i32([0] * nin), i32([0] * nin)
+    scr = torch.empty(amd.compress_large_scratch_size(nin, n), dtype=torch.uint8, device="cuda")
+    rec = {"case": name, "inputs": nin, "input_bytes": n, "slice": amd.compress_large_slice_size(),
+           "periods": []}
+    gibs = lambda ms: round(total / (ms * 1e-3) / (1 << 30), 2)
+    size0 = None
+    for R in (0,) + DECODE_R:
+        nseg = amd.large_index_segments(n, R)
+        index = torch.zeros((nin, amd.large_index_size(n, R)), dtype=torch.uint8, device="cuda")
+        amd.compress_large_indexed_ptr_batch(sptr, sizes, dptr, caps, res, n, R, index=index,
+                                             scratch=scr)
+        torch.cuda.synchronize()
+        rs = res.cpu().tolist()
+        assert min(rs) > 0, rs
+        if R == 0:
+            size0 = sum(rs)
+            continue
+
+        def check(what):
+            torch.cuda.synchronize()
+            assert dres.cpu().tolist() == [n] * nin, (what, dres.cpu().tolist())
+            assert torch.equal(back, flat), what
+            back.zero_()
+
+        indexed = lambda: amd.decompress_indexed_ptr_batch(dptr, res, bptr, sizes, index, nseg, dres)
+        plain = lambda: amd.decompress_ptr_batch(dptr, res, bptr, sizes, dres)
+        for what, fn in (("indexed", indexed), ("plain", plain)):   # warm-up, checked
+            fn()
+            check(what)
+        ts = {"indexed": [], "plain": []}
+        for _ in range(reps):   # alternately
+            for what, fn in (("indexed", indexed), ("plain", plain)):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                fn()
+                e1.record()
+                torch.cuda.synchronize()
+                ts[what].append(e0.elapsed_time(e1))
+        med = {k: sorted(v)[len(v) // 2] for k, v in ts.items()}
+        rec["periods"].append({
+            "R": R, "segments": nseg, "ratio": round(total / sum(rs), 4),
+            "ratio_R0": round(total / size0, 4), "ratio_vs_R0": round(size0 / sum(rs), 4),
+            "indexed": {"ms": round(med["indexed"], 3), "GiBps": gibs(med["indexed"]),
+                        "min_ms": round(min(ts["indexed"]), 3), "max_ms": round(max(ts["indexed"]), 3)},
+            "plain": {"ms": round(med["plain"], 3), "GiBps": gibs(med["plain"]),
+                      "min_ms": round(min(ts["plain"]), 3), "max_ms": round(max(ts["plain"]), 3)},
+            "speedup": round(med["plain"] / med["indexed"], 2)})
+    return rec
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "large_compress.json"))
+    ap.add_argument("--decode", action="store_true", help="the decode leg (see above)")
+    ap.add_argument("--out", default=None)
     ap.add_argument("--case", help="run one case in this process (used by the parent)")
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "large_indexed.json" if a.decode else "large_compress.json")
     if a.case:
-        print(json.dumps(run_case(a.case, a.reps)), flush=True)
+        print(json.dumps((run_decode_case if a.decode else run_case)(a.case, a.reps)), flush=True)
         return 0
     recs = []
     for name in CASES:
         try:
             p = subprocess.run([sys.executable, os.path.abspath(__file__), "--case", name,
-                                "--reps", str(a.reps)], capture_output=True, text=True,
-                               timeout=CASE_TIMEOUT)
+                                "--reps", str(a.reps)] + (["--decode"] if a.decode else []),
+                               capture_output=True, text=True, timeout=CASE_TIMEOUT)
         except subprocess.TimeoutExpired:
             print("%s: no result within %d s; stopping" % (name, CASE_TIMEOUT), file=sys.stderr)
             return 1
@@ -179,7 +268,8 @@ def main():
         recs.append(json.loads(line))
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as f:
-        json.dump({"tool": "tools/large_bench.py", "reps": a.reps, "cases": recs}, f, indent=1)
+        json.dump({"tool": "tools/large_bench.py" + (" --decode" if a.decode else ""),
+                   "reps": a.reps, "cases": recs}, f, indent=1)
         f.write("\n")
     return 0
 
