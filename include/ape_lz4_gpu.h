@@ -323,6 +323,75 @@ int APE_LZ4_decompress_safe_indexed_batch_dev(const char *const *d_src,
                                               int maxSegments, int *d_result, int nblocks,
                                               void *stream);
 
+/* ---- byte ranges of indexed blocks (lz4_decode.hip) ----
+ * APE_LZ4_decompress_range_indexed_batch_dev decodes, for each REQUEST, the bytes
+ * [rangeStart, rangeStart + rangeLen) of an indexed block without decoding the block: only the
+ * segments that cover the range are parsed.  The batch dimension is the request; d_src,
+ * d_compressedSize and d_index describe nblocks blocks as in the whole-block call, every
+ * other array has nreq entries, and d_blockOf[r] names request r's block (NULL: request r
+ * reads block r, and nreq == nblocks).  Many requests may name one block; each has its own
+ * d_dst[r].  Two stream-ordered launches, no scratch, no allocation, no sync,
+ * graph-capturable.  The index is never trusted.
+ *
+ * For request r on block i, with n and c from the index, a = d_rangeStart[r] and
+ * m = min(d_rangeLen[r], n - a):
+ *   - d_result[r] = -1 for d_blockOf[r] outside [0, nblocks), a < 0, d_rangeLen[r] < 0, a > n,
+ *     or a header the whole-block call rejects (there is no capacity to compare n with; an
+ *     n >= 2^31 is rejected); APE_LZ4_GPU_ERANGE for nseg > maxSegments; both leave
+ *     d_window = {0, 0};
+ *   - m == 0: d_result[r] = 0, nothing is written, d_window = {0, 0}.
+ * Otherwise the covering segments j0 (of a) and j1 (of a + m - 1) come from this binary search
+ * of the op column, for x = a and x = a + m - 1: lo = 0, hi = nseg; while hi - lo > 1:
+ * mid = (lo + hi) / 2, lo = mid if op_mid <= x, else hi = mid; j = lo.  The request is -1
+ * unless op_j0 <= a < op_{j0+1}, op_j1 <= a + m - 1 < op_{j1+1} and j0 <= j1 (a column that
+ * is not sorted can fail this).
+ *
+ * Final run.  Segment nseg - 1 is ONE FINAL LITERAL RUN when, with L = n - op_last,
+ * c - ip_last == 1 + lenbytes(L) + L (lenbytes(L) = 0 for L < 15, else (L - 15) / 255 + 1) and
+ * the bytes say so: the token's high nibble is min(L, 15), every length byte but the last is
+ * 255 and the last is (L - 15) % 255.  (The closed form alone is met by a segment of
+ * 15-literal, 4-byte-match sequences too.)  When j1 = nseg - 1 is such a run, only its bytes
+ * [max(a, op_last), a + m) are copied: a read from an incompressible block costs its own size.
+ *
+ * Window.  lo = a if j0 is the verified final run, else op_j0.  E = a + m if j1 is the
+ * verified final run, else op_{j1+1}.  hi = min(E + 16, n): the 16 covers the 12 bytes that the
+ * reference's end-of-output tests want after a sequence, so every sequence that ends at or
+ * before E is judged as in mid-block; but hi = E when j0 is the verified final run, where
+ * nothing is decoded and the range is copied (need = m: a 4 KiB read from an incompressible
+ * block takes a 4 KiB destination).  need = hi - lo bytes of d_dst[r] are used:
+ * d_window[2r] = a - lo (where the range begins in d_dst[r]), d_window[2r + 1] = need.
+ * d_dstCap[r] < need gives APE_LZ4_GPU_ERANGE with nothing written: read need from d_window and
+ * retry.  Otherwise the first launch writes d_result[r] = m.
+ *
+ * The second launch is nreq x wavesPerRequest waves (fewer than 2^31): wave k of request r
+ * decodes segments j0 + k, j0 + k + wavesPerRequest, ... up to j1, so wavesPerRequest is a
+ * parallelism knob only.  Segment j is decoded as by the whole-block call -- src + ip_j, the
+ * block's true end, floor op_j, the stop at ip_{j+1}, the same pair checks and success rule --
+ * into d_dst[r] + (op_j - lo) with the output room hi - op_j, whatever d_dstCap[r] is, so a
+ * result never depends on spare capacity.  An op_j outside [lo, hi] fails like a wrong pair
+ * (p = ip_j).  Failures record -(p)-1 with the smallest p, as in the whole-block call.
+ *   - Nothing outside src[0, c), the index and dst[0, need) is accessed, whatever the input.
+ *   - d_result[r] = m > 0: dst[d_window[2r], +m) is what this segment decode of the covering
+ *     segments gives; bytes of dst[0, need) outside it are unspecified.
+ *   - For every (block, index) the whole-block call accepts, that is APE_LZ4_decompress_safe's
+ *     bytes [a, a + m).
+ *   - Segments before j0 are not parsed: a forged index over a valid block can select other
+ *     bytes.  It cannot reach out of bounds.
+ * The decode does not stop inside segment j1 once a + m is reached (that needs another flag
+ * in the decoder's hot loop): a request costs its covering segments, and restartBytes is the
+ * granularity knob.
+ * APE_LZ4_GPU_EINVAL before any device call: a null array (d_blockOf may be NULL only when
+ * nreq == nblocks), a negative count, wavesPerRequest < 1, nreq x wavesPerRequest >= 2^31,
+ * maxSegments < 1, a misaligned index, a stride below 16 + 8 (maxSegments + 1) or no multiple
+ * of 16. */
+int APE_LZ4_decompress_range_indexed_batch_dev(const char *const *d_src,
+                                               const int *d_compressedSize, const void *d_index,
+                                               size_t index_stride, int maxSegments, int nblocks,
+                                               const int *d_blockOf, const int *d_rangeStart,
+                                               const int *d_rangeLen, char *const *d_dst,
+                                               const int *d_dstCap, int *d_window, int *d_result,
+                                               int nreq, int wavesPerRequest, void *stream);
+
 /* One-shot routing: ape_lz4.h one-shot calls on blocks smaller than
  * `bytes` (compress: input size; decompress_safe/_partial: capacity) run the host codec,
  * which is byte-identical to the reference; larger ones run on the GPU.  The default is

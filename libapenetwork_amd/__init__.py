@@ -25,7 +25,7 @@ __all__ = [
     "Chain",
     "compress_large_slice_size", "compress_large_scratch_size", "compress_large_ptr_batch",
     "large_index_segments", "large_index_size", "compress_large_indexed_ptr_batch",
-    "decompress_indexed_ptr_batch",
+    "decompress_indexed_ptr_batch", "decompress_range_indexed_ptr_batch",
     "oneshot_on_gpu",
     "cdict_size", "cdict_window", "cdict_prepare", "compress_cdict_batch",
     "ONESHOT_HOST_ALL",
@@ -91,6 +91,7 @@ def lib():
             "APE_LZ4_large_index_size": (sz, [i, i]),
             "APE_LZ4_compress_large_indexed_batch_dev": (i, [p, p, p, p, p, i, i, i, p, sz, i, p, sz, p]),
             "APE_LZ4_decompress_safe_indexed_batch_dev": (i, [p, p, p, p, p, sz, i, p, i, p]),
+            "APE_LZ4_decompress_range_indexed_batch_dev": (i, [p, p, p, sz, i, i, p, p, p, p, p, p, p, i, i, p]),
             "APE_LZ4_cdict_size": (sz, []),
             "APE_LZ4_cdict_window": (i, [i, i]),
             "APE_LZ4_cdict_prepare_dev": (i, [p, i, i, p, sz, p]),
@@ -506,6 +507,36 @@ def decompress_indexed_ptr_batch(src_ptrs, comp_sizes, dst_ptrs, caps, index, ma
         _ptr(src_ptrs), _ptr(comp_sizes), _ptr(dst_ptrs), _ptr(caps), _ptr(index), stride,
         max_segments, _ptr(results), n, _stream(stream)),
         "APE_LZ4_decompress_safe_indexed_batch_dev")
+
+
+def decompress_range_indexed_ptr_batch(src_ptrs, comp_sizes, index, max_segments, range_starts,
+                                       range_lens, dst_ptrs, caps, window, results, block_of=None,
+                                       waves_per_request=4, stream=None):
+    """Byte ranges of indexed blocks (APE_LZ4_decompress_range_indexed_batch_dev): request r
+    reads range_lens[r] bytes from range_starts[r] of block block_of[r] (None: block r, one
+    request per block) into dst_ptrs[r], decoding only the covering segments.  src_ptrs,
+    comp_sizes and index (uint8 CUDA [blocks, stride]) are per block, every other tensor per
+    request; window is int32 [2 * requests] and receives {where the range begins in dst, the
+    bytes of dst used}; results the bytes read, or a negative code (ERANGE: caps[r] is below
+    window[2r + 1])."""
+    import torch
+    what = "decompress_range_indexed_ptr_batch"
+    _arr(comp_sizes, what + " comp_sizes", torch.int32)
+    _arr(range_starts, what + " range_starts", torch.int32)
+    nb, nreq = comp_sizes.shape[0], range_starts.shape[0]
+    _ptr_args(what, nb, src_ptrs=(src_ptrs, _i64()), comp_sizes=(comp_sizes, _i32()))
+    _ptr_args(what, nreq, range_starts=(range_starts, _i32()), range_lens=(range_lens, _i32()),
+              dst_ptrs=(dst_ptrs, _i64()), caps=(caps, _i32()), results=(results, _i32()),
+              block_of=(block_of, (_i32(), True)))
+    _arr(window, what + " window", torch.int32, 2 * nreq)
+    if block_of is None and nreq != nb:
+        raise ValueError("%s: %d requests for %d blocks need block_of" % (what, nreq, nb))
+    stride = _index_arg(what, index, nb)
+    _check(lib().APE_LZ4_decompress_range_indexed_batch_dev(
+        _ptr(src_ptrs), _ptr(comp_sizes), _ptr(index), stride, max_segments, nb, _ptr(block_of),
+        _ptr(range_starts), _ptr(range_lens), _ptr(dst_ptrs), _ptr(caps), _ptr(window),
+        _ptr(results), nreq, waves_per_request, _stream(stream)),
+        "APE_LZ4_decompress_range_indexed_batch_dev")
 
 
 def cdict_size():

@@ -39,6 +39,8 @@
 // (lz4_decode_indexed_kernel, at the end): the same code with a template flag STOP, under
 // which the parse ends at a given token position instead of the block's final run.  The four
 // instantiations without the flag compile to the device code they had before it existed.
+// A byte range of such a block is read by decoding only the segments that cover it
+// (lz4_range_plan_kernel, lz4_decode_range_kernel, after the indexed kernel).
 #include "lz4_gpu_internal.h"
 #include <type_traits>
 
@@ -1309,6 +1311,204 @@ hipError_t launch_decode_indexed(const IndexedArgs &a, hipStream_t s) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(lz4_decode_indexed_kernel, dim3((unsigned)a.nblocks * (unsigned)a.max_seg),
+                       dim3(64), 0, s, a);
+    return hipGetLastError();
+}
+
+// ---- byte ranges of indexed blocks (include/ape_lz4_gpu.h, "byte ranges of indexed
+// blocks") ----
+// Whether segment nseg - 1, the tokens [ipl, c) for the output [opl, n), is ONE final literal
+// run: the closed form c - ipl == 1 + lenbytes(L) + L with L = n - opl, and the bytes that
+// say so -- the token's literal nibble, every length byte but the last 255, the last the
+// remainder.  (The closed form alone does not: sequences of 15 literals and a 4-byte match
+// cost as many bytes as they produce.)  The length bytes are read 16 per lane, with no early
+// exit.  Called by all 64 lanes with wave-uniform arguments, by the plan launch and by every
+// wave that needs the answer: none depends on what another recorded.  lit0 = where the run's
+// bytes start in src.
+__device__ __forceinline__ bool final_run(gcu8 *src, int csize, uint32_t n, uint32_t ipl,
+                                          uint32_t opl, int lane, uint32_t &lit0) {
+    lit0 = 0;
+    if (csize <= 0 || ipl >= (uint32_t)csize || opl > n) return false;
+    const uint32_t L = n - opl;
+    const uint32_t nb = L < 15u ? 0u : (L - 15u) / 255u + 1u;   // length bytes
+    if ((uint64_t)((uint32_t)csize - ipl) != 1ull + nb + L) return false;
+    bool ok = ((uint32_t)src[ipl] >> 4) == umin(L, 15u);
+    if (nb) {
+        gcu8 *p = src + ipl + 1u;
+        const uint32_t n255 = nb - 1u, q = n255 >> 4;
+        uint32_t k = (uint32_t)lane;
+        for (; k + 192u < q; k += 256u) {   // four 16-byte loads in flight per lane
+            const uint4 v0 = gload16(p + 16u * k), v1 = gload16(p + 16u * (k + 64u));
+            const uint4 v2 = gload16(p + 16u * (k + 128u)), v3 = gload16(p + 16u * (k + 192u));
+            const uint32_t x0 = v0.x & v0.y & v0.z & v0.w, x1 = v1.x & v1.y & v1.z & v1.w;
+            const uint32_t x2 = v2.x & v2.y & v2.z & v2.w, x3 = v3.x & v3.y & v3.z & v3.w;
+            ok &= (x0 & x1 & x2 & x3) == 0xFFFFFFFFu;
+        }
+        for (; k < q; k += 64u) {
+            const uint4 v = gload16(p + 16u * k);
+            ok &= (v.x & v.y & v.z & v.w) == 0xFFFFFFFFu;
+        }
+        const uint32_t t = 16u * q + (uint32_t)lane;
+        if (lane < 16 && t < n255) ok &= p[t] == 255u;
+        ok &= (uint32_t)p[n255] == (L - 15u) % 255u;
+    }
+    lit0 = ipl + 1u + nb;
+    return wave_ballot(!ok) == 0ull;
+}
+
+// The segment of x: the binary search of the op column that the header documents.
+__device__ __forceinline__ uint32_t range_segment(const uint32_t *w, uint32_t nseg, uint32_t x) {
+    uint32_t lo = 0, hi = nseg;
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (w[5 + 2 * (size_t)mid] <= x) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// One request's plan, recomputed by the plan launch and by every wave of the decode launch
+// (the index_header pattern).  All of it is wave-uniform.
+struct RangePlan {
+    int res;             // the request's result so far: < 0 an error, 0 an empty range, else m
+    int win0, need;      // d_window: where the range begins in dst, the bytes of dst it takes
+    gcu8 *src;
+    const uint32_t *w;
+    int csize;
+    uint32_t nseg, n, j0, j1, lo, hi, a, m;
+    uint32_t lit0;       // run: where the final run's bytes start in src
+    bool run;            // segment j1 = nseg - 1 is one verified final literal run
+};
+
+__device__ __forceinline__ void range_plan(const RangeArgs &A, int r, int lane, RangePlan &P) {
+    P.res = -1;
+    P.win0 = 0;
+    P.need = 0;
+    const int i = A.block_of ? A.block_of[r] : r;
+    const int a = A.start[r], len = A.len[r];
+    if ((uint32_t)i >= (uint32_t)A.nblocks || a < 0 || len < 0) return;
+    P.w = (const uint32_t *)(A.index + (size_t)i * A.index_stride);
+    P.csize = A.src_size[i];
+    // (no capacity to compare n with: the largest one, so n < 2^31 and need fits an int)
+    const int e = index_header(P.w, P.csize, 0x7FFFFFFF, A.max_seg);
+    if (e) {
+        P.res = e;
+        return;
+    }
+    P.src = (gcu8 *)A.src[i];
+    P.nseg = P.w[1];
+    P.n = P.w[2];
+    if ((uint32_t)a > P.n) return;
+    P.a = (uint32_t)a;
+    P.m = umin((uint32_t)len, P.n - P.a);
+    if (P.m == 0u) {
+        P.res = 0;
+        return;
+    }
+    const uint32_t x1 = P.a + P.m - 1u;
+    P.j0 = range_segment(P.w, P.nseg, P.a);
+    P.j1 = range_segment(P.w, P.nseg, x1);
+    const uint32_t o0 = P.w[5 + 2 * (size_t)P.j0], o0n = P.w[7 + 2 * (size_t)P.j0];
+    const uint32_t o1 = P.w[5 + 2 * (size_t)P.j1], o1n = P.w[7 + 2 * (size_t)P.j1];
+    // (a column that is not sorted can fail these)
+    if (!(o0 <= P.a && P.a < o0n && o1 <= x1 && x1 < o1n && P.j0 <= P.j1)) return;
+    P.run = P.j1 + 1u == P.nseg &&
+            final_run(P.src, P.csize, P.n, P.w[4 + 2 * (size_t)P.j1], o1, lane, P.lit0);
+    const bool copy_only = P.run && P.j0 == P.j1;   // nothing is decoded: no room after E
+    P.lo = copy_only ? P.a : o0;
+    const uint32_t E = P.run ? P.a + P.m : o1n;
+    // min(E + 16, n), and n when a forged op_{j1+1} lies past it (no sum that could wrap)
+    P.hi = copy_only ? E : (E < P.n && P.n - E > 16u ? E + 16u : P.n);
+    P.win0 = (int)(P.a - P.lo);
+    P.need = (int)(P.hi - P.lo);
+    P.res = A.dst_cap[r] < P.need ? kErange : (int)P.m;
+}
+
+__global__ void __launch_bounds__(64)
+lz4_range_plan_kernel(RangeArgs a) {
+    const int r = (int)blockIdx.x, lane = (int)threadIdx.x;
+    RangePlan P;
+    range_plan(a, r, lane, P);
+    if (lane == 0) {
+        a.result[r] = P.res;
+        a.window[2 * (size_t)r] = P.win0;
+        a.window[2 * (size_t)r + 1] = P.need;
+    }
+}
+
+// Wave k of request r decodes segments j0 + k, j0 + k + waves, ... <= j1 of the request's
+// block into dst + (op_j - lo), each as lz4_decode_indexed_kernel does but with the output
+// room hi - op_j, whatever the capacity; a verified final run is copied instead, the
+// requested bytes only.  op_j outside [lo, hi] (an unsorted column) fails like a wrong pair.
+// Failures go to d_result[r] by the same atomic max.
+__global__ void __launch_bounds__(64)
+lz4_decode_range_kernel(RangeArgs a) {
+    __shared__ WaveLds L;
+    const int r = (int)(blockIdx.x / (uint32_t)a.waves), lane = (int)threadIdx.x;
+    const uint32_t k = blockIdx.x % (uint32_t)a.waves;
+    RangePlan P;
+    range_plan(a, r, lane, P);
+    if (P.res <= 0) return;
+    gu8 *dst = (gu8 *)a.dst[r];
+    for (uint32_t j = P.j0 + k; j <= P.j1; j += (uint32_t)a.waves) {
+        const uint32_t *pr = P.w + 4 + 2 * (size_t)j;
+        const uint32_t ip0 = pr[0], op0 = pr[1], ip1 = pr[2], op1 = pr[3];
+        const bool lastseg = j + 1u == P.nseg;
+        if (lastseg && P.run) {   // run bytes [max(a, op_last), a + m), global -> global
+            const uint32_t from = umax(P.a, op0), cnt = P.a + P.m - from;
+            gcu8 *s = P.src + P.lit0 + (from - op0);
+            gu8 *d = dst + (from - P.lo);
+            const uint32_t n16 = cnt >> 4;
+            uint32_t q = (uint32_t)lane;
+            for (; q + 192u < n16; q += 256u) {   // four 16-byte loads in flight per lane
+                const uint4 v0 = gload16(s + 16u * q), v1 = gload16(s + 16u * (q + 64u));
+                const uint4 v2 = gload16(s + 16u * (q + 128u)), v3 = gload16(s + 16u * (q + 192u));
+                gstore16(d + 16u * q, v0);
+                gstore16(d + 16u * (q + 64u), v1);
+                gstore16(d + 16u * (q + 128u), v2);
+                gstore16(d + 16u * (q + 192u), v3);
+            }
+            for (; q < n16; q += 64u) gstore16(d + 16u * q, gload16(s + 16u * q));
+            for (uint32_t t = 16u * n16 + (uint32_t)lane; t < cnt; t += 64u) d[t] = s[t];
+            continue;
+        }
+        uint32_t p = ip0;   // where a failure is reported (the segment's start unless the parse says)
+        bool ok = true;
+        if (P.nseg > 1u) {   // (one segment: both pairs are the header's, checked by the plan)
+            ok = ip0 <= ip1 && op0 <= op1 && ip1 <= (uint32_t)P.csize && op1 <= P.n &&
+                 (lastseg ? ip0 < ip1 : (ip0 < ip1 || op0 == op1));
+            if (ok && ip0 == ip1) continue;   // an empty segment
+            ok = ok && op0 >= P.lo && op0 <= P.hi;
+        }
+        if (ok) {
+            wave_sync();   // (the LDS of the segment before)
+            Seg sg;
+            sg.src = P.src + ip0;
+            sg.dst = dst + (op0 - P.lo);
+            sg.csize = P.csize - (int)ip0;
+            sg.cap = (int)(P.hi - op0);
+            sg.stop = lastseg ? kNoStop : (int)(ip1 - ip0);
+            const BlockArgs none{};
+            decode_block<false, false, false, true>(L, none, 0, lane, &sg);
+            const int res = sg.res;
+            if (res < 0) {
+                ok = false;
+                p = ip0 + (uint32_t)(-(res + 1));
+            } else {
+                ok = sg.hit == !lastseg && (uint32_t)res == op1 - op0;
+            }
+        }
+        if (!ok && lane == 0)
+            atomicMax((unsigned int *)&a.result[r], ~umin(p, 0x7FFFFFFEu));   // -(p)-1
+    }
+}
+
+hipError_t launch_decode_range(const RangeArgs &a, hipStream_t s) {
+    if (a.nreq <= 0) return hipSuccess;
+    hipLaunchKernelGGL(lz4_range_plan_kernel, dim3((unsigned)a.nreq), dim3(64), 0, s, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(lz4_decode_range_kernel, dim3((unsigned)a.nreq * (unsigned)a.waves),
                        dim3(64), 0, s, a);
     return hipGetLastError();
 }

@@ -269,6 +269,24 @@ struct IndexedArgs {
 };
 // check launch + one wave per (block, segment) (lz4_decode.hip)
 hipError_t launch_decode_indexed(const IndexedArgs &a, hipStream_t s);
+// Byte ranges of indexed blocks: the batch dimension is the request.
+struct RangeArgs {
+    const char *const *src;   // caller's arrays, one entry per block
+    const int *src_size;
+    const char *index;        // block i's index at index + i * index_stride
+    size_t index_stride;
+    int max_seg;              // a block with more segments gets kErange
+    int nblocks;
+    const int *block_of;      // per request from here on; null: request r reads block r
+    const int *start, *len;
+    char *const *dst;
+    const int *dst_cap;
+    int *window;              // two ints per request: {where the range begins in dst, need}
+    int *result;
+    int nreq, waves;          // waves per request
+};
+// plan launch (one wave per request) + nreq x waves waves over the covering segments
+hipError_t launch_decode_range(const RangeArgs &a, hipStream_t s);
 size_t large_scratch_layout(int nblocks, int max_src, LargeArgs *out);
 hipError_t launch_large(const LargeArgs &a, int accel, hipStream_t s, hipEvent_t *ev = nullptr);
 hipError_t launch_synth(char *out, size_t stride, int n, long long first, int nblocks,

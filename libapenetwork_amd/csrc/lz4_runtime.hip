@@ -597,6 +597,55 @@ int APE_LZ4_decompress_safe_indexed_batch_dev(const char *const *d_src,
                          "lz4_index_check_kernel + lz4_decode_indexed_kernel");
 }
 
+int APE_LZ4_decompress_range_indexed_batch_dev(const char *const *d_src,
+                                               const int *d_compressedSize, const void *d_index,
+                                               size_t index_stride, int maxSegments, int nblocks,
+                                               const int *d_blockOf, const int *d_rangeStart,
+                                               const int *d_rangeLen, char *const *d_dst,
+                                               const int *d_dstCap, int *d_window, int *d_result,
+                                               int nreq, int wavesPerRequest, void *stream) {
+    if (nblocks < 0 || nreq < 0 || (!d_blockOf && nreq != nblocks) ||
+        (nblocks > 0 && (!d_src || !d_compressedSize || !d_index)) ||
+        (nreq > 0 && (!d_rangeStart || !d_rangeLen || !d_dst || !d_dstCap || !d_window ||
+                      !d_result))) {
+        snprintf(g_err, sizeof g_err, "decompress_range_indexed: invalid argument (a null array, "
+                 "a negative count, or no d_blockOf with nreq %d != nblocks %d)", nreq, nblocks);
+        return APE_LZ4_GPU_EINVAL;
+    }
+    // nreq x wavesPerRequest waves in a one-dimensional grid; the stride holds the header and
+    // maxSegments + 1 pairs, so a block's index is never read past
+    if (wavesPerRequest < 1 || (long long)nreq * wavesPerRequest > 0x7FFFFFFFll ||
+        maxSegments < 1 || ((uintptr_t)d_index & 15u) || index_stride % 16u ||
+        index_stride < 16u + 8u * ((size_t)maxSegments + 1u)) {
+        snprintf(g_err, sizeof g_err, "decompress_range_indexed: %d requests x %d waves, "
+                 "maxSegments %d, index at %p with stride %zu (need wavesPerRequest >= 1, fewer "
+                 "than 2^31 waves in all, maxSegments >= 1, 16-byte alignment and a stride that "
+                 "is a multiple of 16 and >= 16 + 8 (maxSegments + 1))",
+                 nreq, wavesPerRequest, maxSegments, d_index, index_stride);
+        return APE_LZ4_GPU_EINVAL;
+    }
+    int rc = check_device();
+    if (rc) return rc;
+    RangeArgs a{};
+    a.src = d_src;
+    a.src_size = d_compressedSize;
+    a.index = (const char *)d_index;
+    a.index_stride = index_stride;
+    a.max_seg = maxSegments;
+    a.nblocks = nblocks;
+    a.block_of = d_blockOf;
+    a.start = d_rangeStart;
+    a.len = d_rangeLen;
+    a.dst = d_dst;
+    a.dst_cap = d_dstCap;
+    a.window = d_window;
+    a.result = d_result;
+    a.nreq = nreq;
+    a.waves = wavesPerRequest;
+    return finish_launch(launch_decode_range(a, (hipStream_t)stream),
+                         "lz4_range_plan_kernel + lz4_decode_range_kernel");
+}
+
 int APE_LZ4_compress_large_batch_dev(const char *const *d_src, const int *d_srcSize,
                                      char *const *d_dst, const int *d_dstCap, int *d_result,
                                      int nblocks, int maxSrcSize, int acceleration,

@@ -22,9 +22,21 @@ R in {128 KiB, 256 KiB, 1 MiB}, compress_large_indexed, then
 both decoders warmed up, then timed alternately (HIP events, median of --reps each); the
 output of each is compared with the source.
 
+--range reads byte ranges instead (profiles/large_range.json): 16 x 16 MiB of App. C blocks, of
+the torch/lib slice and of random bytes, compress_large_indexed at R = 256 KiB, then
+decompress_range_indexed_ptr_batch for
+
+  4KiB     4096 requests of 4 KiB at random offsets of random blocks
+  1MiB     256 requests of 1 MiB
+  whole    one request (0, n) per block
+
+each sized by the documented retry (capacity 0 gives ERANGE and need), warmed up, compared with
+the source, then timed by HIP events (median of 7) alternately with decompress_indexed_ptr_batch
+of the same blocks -- the only other way to those bytes.
+
 Each case runs in a child process of its own under a time limit; the first failure ends the
 run.  Prints one JSON line per case and writes profiles/large_compress.json (--out).
-usage: large_bench.py [--decode] [--reps 5] [--out FILE] [--case NAME]"""
+usage: large_bench.py [--decode | --range] [--reps 5] [--out FILE] [--case NAME]"""
 import argparse
 import ctypes as C
 import glob
@@ -158,6 +170,10 @@ def fill(torch, np, kind, flat, n):
     import libapenetwork_amd as amd
     if kind == "appC":
         amd.synth_blocks(flat.view(-1, 65536), 65536, 0, 1)
+    elif kind == "rand":
+        g = torch.Generator(device="cuda")
+        g.manual_seed(20264)
+        flat[:] = torch.randint(0, 256, (flat.numel(),), dtype=torch.uint8, device="cuda", generator=g)
     elif kind == "pysrc":   # ratio_files.py's other corpus: 4 MiB of Python sources, repeated
         py = b"".join(open(f, "rb").read() for f in sorted(glob.glob("/usr/lib/python3.10/*.py")))
         assert len(py) >= n, "Python sources shorter than 4 MiB"
@@ -239,23 +255,121 @@ def run_decode_case(name, reps):
     return rec
 
 
+RANGE_CASES = {"appC_16x16MiB": ("appC", 16, 16 * MB), "sobin_16x16MiB": ("sobin", 16, 16 * MB),
+               "rand_16x16MiB": ("rand", 16, 16 * MB)}
+RANGE_R = 256 << 10
+RANGE_REPS = 7
+# name: (requests, bytes each (0: the whole block), waves per request)
+RANGE_MODES = {"4KiB": (4096, 4096, 2), "1MiB": (256, MB, 6), "whole": (0, 0, 64)}
+
+
+def run_range_case(name, reps):
+    import numpy as np
+    import torch
+    import libapenetwork_amd as amd
+    kind, nin, n = RANGE_CASES[name]
+    total, R = nin * n, RANGE_R
+    flat = torch.empty(total, dtype=torch.uint8, device="cuda")
+    fill(torch, np, kind, flat, n)
+    i32 = lambda xs: torch.tensor(xs, dtype=torch.int32, device="cuda")
+    i64 = lambda xs: torch.tensor(xs, dtype=torch.int64, device="cuda")
+    bound = amd.compressBound(n)
+    slot = (bound + 15) // 16 * 16
+    out = torch.empty(nin * slot, dtype=torch.uint8, device="cuda")
+    back = torch.empty(total, dtype=torch.uint8, device="cuda")
+    sptr = i64([flat.data_ptr() + i * n for i in range(nin)])
+    dptr = i64([out.data_ptr() + i * slot for i in range(nin)])
+    bptr = i64([back.data_ptr() + i * n for i in range(nin)])
+    sizes, caps, res, dres = i32([n] * nin), i32([bound] * nin), i32([0] * nin), i32([0] * nin)
+    scr = torch.empty(amd.compress_large_scratch_size(nin, n), dtype=torch.uint8, device="cuda")
+    nseg = amd.large_index_segments(n, R)
+    index = torch.zeros((nin, amd.large_index_size(n, R)), dtype=torch.uint8, device="cuda")
+    amd.compress_large_indexed_ptr_batch(sptr, sizes, dptr, caps, res, n, R, index=index, scratch=scr)
+    torch.cuda.synchronize()
+    rs = res.cpu().tolist()
+    assert min(rs) > 0, rs
+    rec = {"case": name, "inputs": nin, "input_bytes": n, "R": R, "segments": nseg,
+           "ratio": round(total / sum(rs), 4), "reps": reps, "modes": {}}
+
+    def whole():
+        amd.decompress_indexed_ptr_batch(dptr, res, bptr, sizes, index, nseg, dres)
+    whole()
+    torch.cuda.synchronize()
+    assert dres.cpu().tolist() == [n] * nin and torch.equal(back, flat), "whole-block decode"
+    rng = np.random.default_rng(20264)
+    for mode, (nreq, size, waves) in RANGE_MODES.items():
+        if nreq:
+            blk = rng.integers(0, nin, nreq).tolist()
+            st = rng.integers(0, n - size + 1, nreq).tolist()
+        else:
+            nreq, size, blk, st = nin, n, list(range(nin)), [0] * nin
+        block_of, starts, lens = i32(blk), i32(st), i32([size] * nreq)
+        win, rres = i32([0] * (2 * nreq)), i32([0] * nreq)
+        none = i64([0] * nreq)
+
+        def read(dst, rcaps):
+            amd.decompress_range_indexed_ptr_batch(dptr, res, index, nseg, starts, lens, dst, rcaps,
+                                                   win, rres, block_of=block_of,
+                                                   waves_per_request=waves)
+        read(none, i32([0] * nreq))   # the documented retry: ERANGE and the bytes needed
+        torch.cuda.synchronize()
+        assert rres.cpu().tolist() == [amd.ERANGE] * nreq
+        need = win.cpu().tolist()[1::2]
+        offs = np.concatenate(([0], np.cumsum([(c + 15) // 16 * 16 for c in need]))).tolist()
+        buf = torch.empty(offs[-1], dtype=torch.uint8, device="cuda")
+        rptr, rcaps = i64([buf.data_ptr() + o for o in offs[:-1]]), i32(need)
+        read(rptr, rcaps)             # warm-up, checked
+        torch.cuda.synchronize()
+        assert rres.cpu().tolist() == [size] * nreq, mode
+        w0 = win.cpu().tolist()[0::2]
+        for q in range(nreq):
+            got = buf[offs[q] + w0[q]:offs[q] + w0[q] + size]
+            assert torch.equal(got, flat[blk[q] * n + st[q]:blk[q] * n + st[q] + size]), (mode, q)
+        ts = {"range": [], "whole": []}
+        for _ in range(reps):   # alternately
+            for what, fn in (("range", lambda: read(rptr, rcaps)), ("whole", whole)):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                fn()
+                e1.record()
+                torch.cuda.synchronize()
+                ts[what].append(e0.elapsed_time(e1))
+        med = {k: sorted(v)[len(v) // 2] for k, v in ts.items()}
+        rec["modes"][mode] = {
+            "requests": nreq, "bytes_each": size, "waves_per_request": waves,
+            "need_bytes": int(sum(need)), "need_max": int(max(need)),
+            "range_ms": round(med["range"], 4), "range_min_ms": round(min(ts["range"]), 4),
+            "range_max_ms": round(max(ts["range"]), 4),
+            "whole_blocks_ms": round(med["whole"], 4), "whole_min_ms": round(min(ts["whole"]), 4),
+            "whole_max_ms": round(max(ts["whole"]), 4),
+            "range_vs_whole": round(med["range"] / med["whole"], 4)}
+        del buf
+    return rec
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--decode", action="store_true", help="the decode leg (see above)")
+    ap.add_argument("--range", action="store_true", dest="ranges", help="the range leg (see above)")
     ap.add_argument("--out", default=None)
     ap.add_argument("--case", help="run one case in this process (used by the parent)")
     a = ap.parse_args()
+    leg = "--range" if a.ranges else "--decode" if a.decode else ""
+    if a.ranges:
+        a.reps = RANGE_REPS
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "large_indexed.json" if a.decode else "large_compress.json")
+        a.out = os.path.join(ROOT, "profiles", {"--range": "large_range.json", "--decode": "large_indexed.json",
+                                                "": "large_compress.json"}[leg])
     if a.case:
-        print(json.dumps((run_decode_case if a.decode else run_case)(a.case, a.reps)), flush=True)
+        run = {"--range": run_range_case, "--decode": run_decode_case, "": run_case}[leg]
+        print(json.dumps(run(a.case, a.reps)), flush=True)
         return 0
     recs = []
-    for name in CASES:
+    for name in (RANGE_CASES if a.ranges else CASES):
         try:
             p = subprocess.run([sys.executable, os.path.abspath(__file__), "--case", name,
-                                "--reps", str(a.reps)] + (["--decode"] if a.decode else []),
+                                "--reps", str(a.reps)] + ([leg] if leg else []),
                                capture_output=True, text=True, timeout=CASE_TIMEOUT)
         except subprocess.TimeoutExpired:
             print("%s: no result within %d s; stopping" % (name, CASE_TIMEOUT), file=sys.stderr)
@@ -268,7 +382,7 @@ def main():
         recs.append(json.loads(line))
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as f:
-        json.dump({"tool": "tools/large_bench.py" + (" --decode" if a.decode else ""),
+        json.dump({"tool": ("tools/large_bench.py " + leg).strip(),
                    "reps": a.reps, "cases": recs}, f, indent=1)
         f.write("\n")
     return 0
