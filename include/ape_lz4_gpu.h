@@ -198,6 +198,39 @@ int APE_LZ4_compress_destSize_batch_scratch_dev(const char *const *d_src, int *d
                                                 int *d_result, int nblocks, void *d_scratch,
                                                 size_t scratch_bytes, void *stream);
 
+/* ---- high-ratio mode: spend time, get ratio (lz4_encode_hc.hip) ----
+ * d_result[i] <- size of one valid LZ4 v1.7.1 block of d_src[i][0, d_srcSize[i]) (decodes with
+ * decompress_safe, cap = srcSize; never above compressBound(srcSize)), found by a deep search:
+ * every position tries the first `depth` earlier positions that share the hash of its 4 bytes,
+ * nearest first, keeps the strictly longest match, and a sequential parse takes the match at
+ * the first position whose successor's match is not longer (a one-step lazy parse).  Per block
+ * the call behaves as APE_LZ4_compress_batch_dev: 0 if the block does not fit d_dstCap[i]
+ * (checked before every sequence is written) or the size is negative, APE_LZ4_GPU_ERANGE for
+ * d_srcSize[i] > 65536; the other blocks of the call are unaffected; nothing outside
+ * d_dst[i][0, cap) is written and nothing outside d_src[i][0, size) is read.
+ *
+ * depth : chain candidates tried per position, 1..256; 0 means the default, 64.  The ratio
+ *   grows and the speed falls with it (README, "high-ratio mode").
+ * DETERMINISM: the output bytes are a pure function of (input bytes, depth) -- the same on
+ *   every call, stream, batch composition, scratch size and alignment; tests/hcmodel.py
+ *   defines that function on the CPU.  The bytes differ from the reference's and from
+ *   APE_LZ4_compress_batch_dev's.
+ * scratch : the caller's, 16-byte aligned device memory.  scratch_size(nblocks) is what one
+ *   pass over nblocks takes -- a chain table and one (length, source) record per position,
+ *   393216 bytes per block, at most 1024 blocks at a time; 0 for nblocks <= 0.  A smaller
+ *   scratch, at least scratch_size(1), makes the call run several passes with identical
+ *   output.  Every scratch byte the call reads it has written before, in the same call.
+ * Asynchronous, no allocation, no sync, graph-capturable: three stream-ordered launches per
+ * pass, their number decided on the host.  APE_LZ4_GPU_EINVAL before any device call for
+ * nblocks < 0, a null array (nblocks > 0), depth outside 0..256, a null or misaligned
+ * scratch or one below scratch_size(1); with nblocks == 0 it returns 0 and launches
+ * nothing. */
+size_t APE_LZ4_compress_hc_scratch_size(int nblocks);
+int APE_LZ4_compress_hc_batch_dev(const char *const *d_src, const int *d_srcSize,
+                                  char *const *d_dst, const int *d_dstCap, int *d_result,
+                                  int nblocks, int depth, void *d_scratch, size_t scratch_bytes,
+                                  void *stream);
+
 /* ---- inputs larger than one encoder block, as ONE LZ4 block (lz4_large.hip) ----
  * == N x APE_LZ4_compress_fast on inputs of any size up to maxSrcSize: d_result[i] <-
  * size of ONE valid LZ4 block of d_src[i][0, d_srcSize[i]) (decodes with decompress_safe,

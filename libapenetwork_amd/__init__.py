@@ -28,6 +28,7 @@ __all__ = [
     "decompress_indexed_ptr_batch", "decompress_range_indexed_ptr_batch",
     "oneshot_on_gpu",
     "cdict_size", "cdict_window", "cdict_prepare", "compress_cdict_batch",
+    "compress_hc_scratch_size", "compress_hc_ptr_batch",
     "ONESHOT_HOST_ALL",
 ]
 
@@ -96,6 +97,8 @@ def lib():
             "APE_LZ4_cdict_window": (i, [i, i]),
             "APE_LZ4_cdict_prepare_dev": (i, [p, i, i, p, sz, p]),
             "APE_LZ4_compress_usingCDict_batch_dev": (i, [p, p, p, p, p, i, p, p]),
+            "APE_LZ4_compress_hc_scratch_size": (sz, [i]),
+            "APE_LZ4_compress_hc_batch_dev": (i, [p, p, p, p, p, i, i, p, sz, p]),
             "APE_LZ4_rxbuf_new": (p, [sz]),
             "APE_LZ4_rxbuf_prepare": (i, [p, sz]),
             "APE_LZ4_rxbuf_append": (i, [p, p, sz]),
@@ -576,6 +579,28 @@ def compress_cdict_batch(src_ptrs, src_sizes, dst_ptrs, caps, results, cdict, st
     _check(lib().APE_LZ4_compress_usingCDict_batch_dev(
         _ptr(src_ptrs), _ptr(src_sizes), _ptr(dst_ptrs), _ptr(caps), _ptr(results), n,
         _ptr(cdict), _stream(stream)), "APE_LZ4_compress_usingCDict_batch_dev")
+
+
+def compress_hc_scratch_size(nblocks):
+    """APE_LZ4_compress_hc_scratch_size: scratch bytes for one pass over nblocks."""
+    return lib().APE_LZ4_compress_hc_scratch_size(nblocks)
+
+
+def compress_hc_ptr_batch(src_ptrs, src_sizes, dst_ptrs, caps, results, depth, scratch,
+                          stream=None):
+    """The high-ratio mode, pointer-array form (int64 tensors of pointers): depth chain
+    candidates per position (1..256, 0 = the default 64); scratch is a uint8 CUDA tensor of at
+    least compress_hc_scratch_size(1) bytes (fewer than compress_hc_scratch_size(N): several
+    passes, same bytes).  Allocates nothing, so it can be graph-captured."""
+    import torch
+    _arr(src_sizes, "compress_hc_ptr_batch src_sizes", torch.int32)
+    n = src_sizes.shape[0]
+    _ptr_args("compress_hc_ptr_batch", n, src_ptrs=(src_ptrs, _i64()), src_sizes=(src_sizes, _i32()),
+              dst_ptrs=(dst_ptrs, _i64()), caps=(caps, _i32()), results=(results, _i32()))
+    _arr(scratch, "compress_hc_ptr_batch scratch", torch.uint8)
+    _check(lib().APE_LZ4_compress_hc_batch_dev(
+        _ptr(src_ptrs), _ptr(src_sizes), _ptr(dst_ptrs), _ptr(caps), _ptr(results), n, depth,
+        _ptr(scratch), scratch.numel(), _stream(stream)), "APE_LZ4_compress_hc_batch_dev")
 
 
 def decompress_dict_batch(src_ptrs, comp_sizes, dst_ptrs, caps, dict_ptrs, dict_sizes, results,

@@ -213,6 +213,29 @@ hipError_t launch_cdict_prepare(const char *dict, int dict_size, int max_src, vo
                                 hipStream_t s);
 // the greedy-exact mode (lz4_encode_exact.hip): the reference's sequential parse, byte for byte
 hipError_t launch_encode_exact(const BlockArgs &a, hipStream_t s);
+// The high-ratio mode (lz4_encode_hc.hip; tests/hcmodel.py restates the two constants): hash
+// chains over the block, the first `depth` chain members of every position searched for the
+// longest match, then a sequential parse with a one-step lazy rule.
+constexpr int kHcCap = 272;       // longest match the search reports (the parse extends it)
+constexpr int kHcHashBits = 14;   // chain hash; the u16 head table is 32 KiB of LDS
+constexpr int kHcMaxDepth = 256, kHcDefaultDepth = 64;
+// scratch of one block: chain[p] (u16: nearest earlier position with p's hash, + 1; 0 = none)
+// and match[p] (u32: length << 16 | source; 0 = none) for every position
+constexpr size_t kHcChainBytes = (size_t)kMaxBlock * sizeof(uint16_t);
+constexpr size_t kHcSlotBytes = kHcChainBytes + (size_t)kMaxBlock * sizeof(uint32_t);
+struct HcArgs {
+    const char *const *src;   // caller's arrays, one entry per block of this pass
+    const int *src_size;
+    char *const *dst;
+    const int *dst_cap;
+    int *result;
+    int nblocks, depth;
+    uint16_t *chain;          // block i's at chain + i * kMaxBlock ...
+    uint32_t *match;          // ... and match + i * kMaxBlock
+};
+// chain build (one wave per block), search (one lane per position), parse + emit (one wave per
+// block)
+hipError_t launch_encode_hc(const HcArgs &a, hipStream_t s);
 // compress_destSize pass 2 (lz4_destsize.hip): scratch slot i (at scratch + i*stride, encoder
 // result sres[i]) -> dst[i] cut to target[i]; src_size[i] <- consumed input
 hipError_t launch_destsize(const char *const *src, int *src_size, char *const *dst,

@@ -514,6 +514,51 @@ int APE_LZ4_compress_destSize_batch_dev(const char *const *d_src, int *d_srcSize
     return finish_launch(e, "lz4_encode_kernel + lz4_destsize_kernel");
 }
 
+// ---- the high-ratio mode (lz4_encode_hc.hip) ----
+namespace {
+constexpr int kHcSub = 1024;   // blocks per scratch pass: 262144 search workgroups
+}
+
+size_t APE_LZ4_compress_hc_scratch_size(int nblocks) {
+    if (nblocks <= 0) return 0;
+    return (size_t)(nblocks < kHcSub ? nblocks : kHcSub) * kHcSlotBytes;
+}
+
+int APE_LZ4_compress_hc_batch_dev(const char *const *d_src, const int *d_srcSize,
+                                  char *const *d_dst, const int *d_dstCap, int *d_result,
+                                  int nblocks, int depth, void *d_scratch, size_t scratch_bytes,
+                                  void *stream) {
+    if (nblocks < 0 || depth < 0 || depth > kHcMaxDepth || !d_scratch ||
+        ((uintptr_t)d_scratch & 15u) || scratch_bytes < kHcSlotBytes ||
+        (nblocks > 0 && (!d_src || !d_srcSize || !d_dst || !d_dstCap || !d_result))) {
+        snprintf(g_err, sizeof g_err, "compress_hc: nblocks %d, depth %d (0..%d), scratch of %zu "
+                 "bytes at %p (need %zu bytes, 16-byte aligned)", nblocks, depth, kHcMaxDepth,
+                 scratch_bytes, d_scratch, kHcSlotBytes);
+        return APE_LZ4_GPU_EINVAL;
+    }
+    int rc = check_device();
+    if (rc) return rc;
+    // as many blocks per pass as the caller's scratch holds
+    const size_t fit = scratch_bytes / kHcSlotBytes;
+    int sub = fit < (size_t)kHcSub ? (int)fit : kHcSub;
+    if (sub > nblocks) sub = nblocks;
+    hipError_t e = hipSuccess;
+    for (int off = 0; off < nblocks && e == hipSuccess; off += sub) {
+        HcArgs a{};
+        a.src = d_src + off;
+        a.src_size = d_srcSize + off;
+        a.dst = d_dst + off;
+        a.dst_cap = d_dstCap + off;
+        a.result = d_result + off;
+        a.nblocks = nblocks - off < sub ? nblocks - off : sub;
+        a.depth = depth ? depth : kHcDefaultDepth;
+        a.chain = (uint16_t *)d_scratch;
+        a.match = (uint32_t *)((char *)d_scratch + (size_t)sub * kHcChainBytes);
+        e = launch_encode_hc(a, (hipStream_t)stream);
+    }
+    return finish_launch(e, "lz4_hc_chain_kernel + lz4_hc_search_kernel + lz4_hc_parse_kernel");
+}
+
 // ---- inputs of any size as one block (lz4_large.hip) ----
 namespace {
 constexpr int kLargeMaxSrc = 0x7E000000;   // LZ4_MAX_INPUT_SIZE (ref src/ape_lz4.h)
