@@ -61,7 +61,15 @@ const char *APE_LZ4_gpu_arch(void);         /* "gfx950" */
 /* ---- batched, device-resident, pointer-array form ----
  * d_src[i]  : block i input (device)     d_srcSize[i] : its size (0..65536)
  * d_dst[i]  : block i output (device)    d_dstCap[i]  : its capacity
- * d_result[i] <- compressed size, or 0 if it does not fit d_dstCap[i]. */
+ * d_result[i] <- compressed size, or 0 if it does not fit d_dstCap[i].
+ *
+ * DETERMINISM (APE_LZ4_compress_batch_dev, _compress_fast_batch_dev and
+ *   _compress_withPrefix_batch_dev): the output bytes are a pure function of (input bytes, the
+ *   used prefix, acceleration) -- the same on every call, stream, batch composition, capacity
+ *   that holds the block, and alignment of source and destination; tests/encmodel.py defines
+ *   that function on the CPU.  The strided and host-buffer forms, compress_destSize with a
+ *   target the block fits and the large-input path up to 65536 bytes write the same bytes.  The
+ *   bytes differ from the reference's. */
 int APE_LZ4_compress_batch_dev(const char *const *d_src, const int *d_srcSize,
                                char *const *d_dst, const int *d_dstCap, int *d_result,
                                int nblocks, void *stream);

@@ -14,8 +14,11 @@ the bound, bound - 1, 0 and random values, through two product entry points:
     0 .. 64 KiB of the stream before them as history, every block decoded by the oracle's
     decompress_safe_usingDict with that history to the chunk.
 Canaries around every dst slot are checked per batch (nothing written outside dst[0:cap)).
+With --model K the bytes of every K-th block of the chunk encoder and of the withPrefix chunks
+are also compared with tests/encmodel.py (the definition of the fast encoder's output; the
+pytest suite holds the kernel to it in tests/test_gpu_encode_model.py).
 
-  python3 tests/fuzz/gpu_encode_fuzz.py SECONDS [SEED]
+  python3 tests/fuzz/gpu_encode_fuzz.py SECONDS [SEED] [--model K]
 prints one progress line per batch and a JSON summary; exit 1 on the first mismatch."""
 import ctypes
 import json
@@ -52,15 +55,21 @@ def fail(what, **kw):
 
 
 def main():
-    seconds = float(sys.argv[1]) if len(sys.argv) > 1 else 60.0
-    seed = int(sys.argv[2]) if len(sys.argv) > 2 else 20261
+    argv, every = sys.argv[1:], 0
+    if "--model" in argv:
+        at = argv.index("--model")
+        every = int(argv[at + 1])
+        del argv[at:at + 2]
+        import encmodel
+    seconds = float(argv[0]) if len(argv) > 0 else 60.0
+    seed = int(argv[1]) if len(argv) > 1 else 20261
     import torch
     import libapenetwork_amd as amd
     if not torch.cuda.is_available():
         sys.exit("no GPU")
     orc = ctypes.CDLL(os.path.join(os.path.dirname(TESTS), "oracle", "liblz4_oracle.so"))
     rng = random.Random(seed)
-    t0, nb, checked = time.time(), 0, {"chunk": 0, "exact": 0, "prefix": 0}
+    t0, nb, checked = time.time(), 0, {"chunk": 0, "exact": 0, "prefix": 0, "model": 0}
     while time.time() - t0 < seconds:
         srcs = [block(rng) for _ in range(1000)]
         accel = rng.choice([1, 1, 1, 2, 8])
@@ -92,6 +101,11 @@ def main():
                     continue
                 if r < 0 or r > max(cap, 0):
                     fail("range", **info)
+                if every and i % every == 0:
+                    mr, mc = encmodel.compress(s, cap, acceleration=accel)
+                    if r != mr or out != mc:
+                        fail("model", model=mr, **info)
+                    checked["model"] += 1
                 if len(s) == 0:
                     er, _ = orc_compress(orc, s, cap=cap, accel=accel)
                     if r != er:
@@ -137,6 +151,11 @@ def main():
                                                        ln, d, pr)
                 if dr != ln or o.raw[:ln] != plain[st:st + ln]:
                     fail("prefix roundtrip", decoded=dr, **info)
+                if every and i % every == 0:
+                    mc = encmodel.encode(plain[st:st + ln], plain[st - pr:st])
+                    if comp != mc:
+                        fail("prefix model", model=len(mc), **info)
+                    checked["model"] += 1
             check_canaries()
             checked["prefix"] += len(starts)
         nb += 1
