@@ -238,6 +238,22 @@ int APE_LZ4_compress_hc_batch_dev(const char *const *d_src, const int *d_srcSize
                                   char *const *d_dst, const int *d_dstCap, int *d_result,
                                   int nblocks, int depth, void *d_scratch, size_t scratch_bytes,
                                   void *stream);
+/* The high-ratio mode with history: block i is compressed with the bytes just before d_src[i]
+ * as its history, and decodes with decompress_safe_usingDict given that history (or in place
+ * behind it).  USED HISTORY: the last min(d_prefixSize[i], 65536 - d_srcSize[i]) bytes before
+ * the block -- not rounded to a multiple of 64 as the fast encoder's prefix is; a negative
+ * prefix counts as 0, a null d_prefixSize means no history for any block, and the call then
+ * writes APE_LZ4_compress_hc_batch_dev's bytes.  The chains run over history + block, so a
+ * candidate may lie in the history; only the block's positions are searched and parsed.  A
+ * block shorter than 13 bytes is one literal run.  Nothing outside [d_src[i] - used history,
+ * d_src[i] + size) is read.  Scratch, passes, depth, results and errors are as above.
+ * DETERMINISM: the bytes are a pure function of (input bytes, used history, depth);
+ * tests/hclargemodel.py compress_prefix() defines that function on the CPU. */
+int APE_LZ4_compress_hc_withPrefix_batch_dev(const char *const *d_src, const int *d_srcSize,
+                                             const int *d_prefixSize, char *const *d_dst,
+                                             const int *d_dstCap, int *d_result, int nblocks,
+                                             int depth, void *d_scratch, size_t scratch_bytes,
+                                             void *stream);
 
 /* ---- inputs larger than one encoder block, as ONE LZ4 block (lz4_large.hip) ----
  * == N x APE_LZ4_compress_fast on inputs of any size up to maxSrcSize: d_result[i] <-
@@ -363,6 +379,49 @@ int APE_LZ4_decompress_safe_indexed_batch_dev(const char *const *d_src,
                                               const void *d_index, size_t index_stride,
                                               int maxSegments, int *d_result, int nblocks,
                                               void *stream);
+
+/* ---- large and indexed blocks in the high-ratio mode (lz4_large.hip, lz4_encode_hc.hip) ----
+ * APE_LZ4_compress_large_hc_batch_dev is APE_LZ4_compress_large_indexed_batch_dev with the
+ * high-ratio encoder on the slices: the same slicing at multiples of S, the same restart
+ * points (restartBytes) and seek index (d_index, nullable), the same stitch, the same per-block
+ * results (0 for a negative size or a block that does not fit -- nothing is written then for
+ * an input above 65536 bytes, a smaller one is encoded in place -- and APE_LZ4_GPU_ERANGE above
+ * maxSrcSize), and blocks that every decoder above reads.  Slice k is
+ * compressed as APE_LZ4_compress_hc_withPrefix_batch_dev does with the bytes back to the
+ * input's start or the last restart point as its prefix, so its used history is the last
+ * min(that, 65536 - len_k) bytes.  An input of at most 65536 bytes is one slice and gets
+ * exactly APE_LZ4_compress_hc_batch_dev's bytes.  depth is as there (0..256, 0 = 64).
+ * DETERMINISM: the bytes are a pure function of (input bytes, used history, depth,
+ *   restartBytes) -- the same on every call, stream, batch composition, scratch size and
+ *   alignment; tests/hclargemodel.py is that function (compress_large()).
+ * scratch : the caller's, 16-byte aligned.  APE_LZ4_compress_large_hc_scratch_size(nblocks,
+ *   maxSrcSize, passSlices) is the large path's layout plus the high-ratio tables (393216
+ *   bytes each) of passSlices slices; passSlices = 0 means as many as the batch has, at most
+ *   1024.  It returns 0 for arguments out of range and (size_t)-1 for 2^24 slices or more, as
+ *   APE_LZ4_compress_large_scratch_size does.  The call accepts any scratch of at least
+ *   scratch_size(nblocks, maxSrcSize, 1) bytes and runs the high-ratio kernels in passes of as
+ *   many slices as it holds: a smaller scratch means more passes and the same bytes.
+ * Asynchronous, no allocation, no sync, graph-capturable: plan, three launches per pass, offsets,
+ * stitch and (with an index) one more, their number decided on the host.  APE_LZ4_GPU_EINVAL
+ * before any device call for a null array or nblocks < 0, depth outside 0..256, maxSrcSize
+ * outside [1, 0x7E000000], a restartBytes that is neither 0 nor a positive multiple of S, a
+ * misaligned d_index or a bad index_stride, and a null, misaligned or too small scratch
+ * (APE_LZ4_gpu_last_error names the size needed); nblocks == 0 returns 0 and launches nothing. */
+size_t APE_LZ4_compress_large_hc_scratch_size(int nblocks, int maxSrcSize, int passSlices);
+int APE_LZ4_compress_large_hc_batch_dev(const char *const *d_src, const int *d_srcSize,
+                                        char *const *d_dst, const int *d_dstCap, int *d_result,
+                                        int nblocks, int maxSrcSize, int depth, void *d_scratch,
+                                        size_t scratch_bytes, int restartBytes, void *d_index,
+                                        size_t index_stride, void *stream);
+/* Diagnostic (tools/hc_bench.py --large): the same call without an index and with HIP events
+ * around its launches; waits for them and returns ms6[0..6) = plan, chain, search, parse
+ * (each summed over the passes), offsets, stitch in milliseconds.  Synchronous, creates events:
+ * not for graph capture. */
+int APE_LZ4_compress_large_hc_timed_dev(const char *const *d_src, const int *d_srcSize,
+                                        char *const *d_dst, const int *d_dstCap, int *d_result,
+                                        int nblocks, int maxSrcSize, int depth, void *d_scratch,
+                                        size_t scratch_bytes, int restartBytes, void *stream,
+                                        float *ms6);
 
 /* ---- byte ranges of indexed blocks (lz4_decode.hip) ----
  * APE_LZ4_decompress_range_indexed_batch_dev decodes, for each REQUEST, the bytes

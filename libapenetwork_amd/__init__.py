@@ -29,6 +29,7 @@ __all__ = [
     "oneshot_on_gpu",
     "cdict_size", "cdict_window", "cdict_prepare", "compress_cdict_batch",
     "compress_hc_scratch_size", "compress_hc_ptr_batch",
+    "compress_hc_prefix_ptr_batch", "compress_large_hc_scratch_size", "compress_large_hc_ptr_batch",
     "ONESHOT_HOST_ALL",
 ]
 
@@ -99,6 +100,10 @@ def lib():
             "APE_LZ4_compress_usingCDict_batch_dev": (i, [p, p, p, p, p, i, p, p]),
             "APE_LZ4_compress_hc_scratch_size": (sz, [i]),
             "APE_LZ4_compress_hc_batch_dev": (i, [p, p, p, p, p, i, i, p, sz, p]),
+            "APE_LZ4_compress_hc_withPrefix_batch_dev": (i, [p, p, p, p, p, p, i, i, p, sz, p]),
+            "APE_LZ4_compress_large_hc_scratch_size": (sz, [i, i, i]),
+            "APE_LZ4_compress_large_hc_batch_dev": (i, [p, p, p, p, p, i, i, i, p, sz, i, p, sz, p]),
+            "APE_LZ4_compress_large_hc_timed_dev": (i, [p, p, p, p, p, i, i, i, p, sz, i, p, p]),
             "APE_LZ4_rxbuf_new": (p, [sz]),
             "APE_LZ4_rxbuf_prepare": (i, [p, sz]),
             "APE_LZ4_rxbuf_append": (i, [p, p, sz]),
@@ -601,6 +606,63 @@ def compress_hc_ptr_batch(src_ptrs, src_sizes, dst_ptrs, caps, results, depth, s
     _check(lib().APE_LZ4_compress_hc_batch_dev(
         _ptr(src_ptrs), _ptr(src_sizes), _ptr(dst_ptrs), _ptr(caps), _ptr(results), n, depth,
         _ptr(scratch), scratch.numel(), _stream(stream)), "APE_LZ4_compress_hc_batch_dev")
+
+
+def compress_hc_prefix_ptr_batch(src_ptrs, src_sizes, prefix_sizes, dst_ptrs, caps, results, depth,
+                                 scratch, stream=None):
+    """compress_hc_ptr_batch with history: the prefix_sizes[i] bytes just before src_ptrs[i]
+    (int32 CUDA tensor, or None for no history), of which the last min(prefix, 65536 - size)
+    are used; each block decodes with decompress_dict_batch given that history."""
+    import torch
+    what = "compress_hc_prefix_ptr_batch"
+    _arr(src_sizes, what + " src_sizes", torch.int32)
+    n = src_sizes.shape[0]
+    _ptr_args(what, n, src_ptrs=(src_ptrs, _i64()), src_sizes=(src_sizes, _i32()),
+              prefix_sizes=(prefix_sizes, (_i32(), True)), dst_ptrs=(dst_ptrs, _i64()),
+              caps=(caps, _i32()), results=(results, _i32()))
+    _arr(scratch, what + " scratch", torch.uint8)
+    _check(lib().APE_LZ4_compress_hc_withPrefix_batch_dev(
+        _ptr(src_ptrs), _ptr(src_sizes), _ptr(prefix_sizes), _ptr(dst_ptrs), _ptr(caps),
+        _ptr(results), n, depth, _ptr(scratch), scratch.numel(), _stream(stream)),
+        "APE_LZ4_compress_hc_withPrefix_batch_dev")
+
+
+def compress_large_hc_scratch_size(nblocks, max_src_size, pass_slices=0):
+    """APE_LZ4_compress_large_hc_scratch_size: the large path's scratch plus the high-ratio
+    tables of pass_slices slices (0: as many as the batch has, at most 1024)."""
+    return lib().APE_LZ4_compress_large_hc_scratch_size(nblocks, max_src_size, pass_slices)
+
+
+def compress_large_hc_ptr_batch(src_ptrs, src_sizes, dst_ptrs, caps, results, max_src_size, depth,
+                                restart_bytes=0, index=None, scratch=None, stream=None):
+    """compress_large_indexed_ptr_batch in the high-ratio mode (depth as compress_hc_ptr_batch):
+    inputs of any size up to max_src_size, each as ONE LZ4 block, with a restart point every
+    restart_bytes (0: none) and, when index is given, each block's seek index in its row.
+    scratch: uint8 CUDA tensor of at least compress_large_hc_scratch_size(N, max_src_size, 1)
+    bytes, 16-byte aligned (fewer than ..._scratch_size(N, max_src_size): several passes, same
+    bytes); None allocates one for a single pass.  Returns the scratch."""
+    import torch
+    what = "compress_large_hc_ptr_batch"
+    _arr(src_sizes, what + " src_sizes", torch.int32)
+    n = src_sizes.shape[0]
+    _ptr_args(what, n, src_ptrs=(src_ptrs, _i64()), src_sizes=(src_sizes, _i32()),
+              dst_ptrs=(dst_ptrs, _i64()), caps=(caps, _i32()), results=(results, _i32()))
+    stride = 0
+    if index is not None:
+        stride = _index_arg(what, index, n)
+    if scratch is None:
+        need = compress_large_hc_scratch_size(n, max_src_size)
+        if need == 0 or need >= 1 << 63:
+            raise ValueError("%s: max_src_size outside [1, 0x7E000000] or too many slices for "
+                             "one call" % what)
+        scratch = torch.empty(need, dtype=torch.uint8, device=src_sizes.device)
+    else:
+        _arr(scratch, what + " scratch", torch.uint8)
+    _check(lib().APE_LZ4_compress_large_hc_batch_dev(
+        _ptr(src_ptrs), _ptr(src_sizes), _ptr(dst_ptrs), _ptr(caps), _ptr(results), n,
+        max_src_size, depth, _ptr(scratch), scratch.numel(), restart_bytes, _ptr(index), stride,
+        _stream(stream)), "APE_LZ4_compress_large_hc_batch_dev")
+    return scratch
 
 
 def decompress_dict_batch(src_ptrs, comp_sizes, dst_ptrs, caps, dict_ptrs, dict_sizes, results,

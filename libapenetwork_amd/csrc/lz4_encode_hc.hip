@@ -10,6 +10,12 @@
 // The output is a pure function of (input bytes, depth): tests/hcmodel.py is its definition,
 // and the rules below are that model's, line for line.  Every load of the input stays inside
 // src[0, n) and every store inside dst[0, cap).
+//
+// With history (HcArgs::prefix; tests/hclargemodel.py is the definition) the
+// three kernels work on the WINDOW [src - h, src + n), h = min(prefix, 65536 - n) bytes of
+// history and the block: chain[] and match[] are indexed by window position (h + n <= 65536,
+// so position + 1 stays inside u16), the chains run over the whole window, and only the block's
+// positions h .. h + n - 12 are searched and parsed.  Every load stays inside the window.
 #include "lz4_gpu_internal.h"
 
 namespace apelz4 {
@@ -29,6 +35,12 @@ __device__ __forceinline__ uint32_t len_bytes(uint32_t v) { return v >= 15u ? (v
 // leading equal bytes of two little-endian words whose xor is x (x != 0)
 __device__ __forceinline__ uint32_t first_diff(uint32_t x) { return (uint32_t)__builtin_ctz(x) >> 3; }
 
+// bytes of history block b (of 0 <= n <= kMaxBlock bytes) uses: what the caller offers, as far
+// as one window of u16 positions holds it; not rounded, a negative prefix counts as none
+__device__ __forceinline__ int hc_history(const HcArgs &a, int b, int n) {
+    return a.prefix ? max(0, min(a.prefix[b], kMaxBlock - n)) : 0;
+}
+
 }  // namespace
 
 // ---- chain build ----
@@ -37,13 +49,14 @@ __global__ void __launch_bounds__(64) lz4_hc_chain_kernel(HcArgs a) {
     const int b = blockIdx.x, lane = lane_id();
     const int n = a.src_size[b];
     if (n < kMinLength || n > kMaxBlock) return;   // no position can match: nothing is read
-    gcu8 *src = (gcu8 *)a.src[b];
+    const int hist = hc_history(a, b, n);
+    gcu8 *src = (gcu8 *)a.src[b] - hist;           // the window's base
     uint16_t *chain = a.chain + (size_t)b * kMaxBlock;
     for (int i = lane; i < kHcTable / 8; i += 64) ((uint4 *)head)[i] = make_uint4(0u, 0u, 0u, 0u);
     __syncthreads();
     volatile uint16_t *vhead = head;
     const uint64_t below = (1ull << lane) - 1ull;
-    const int last = n - kMinMatch;
+    const int last = hist + n - kMinMatch;
     for (int base = 0; base <= last; base += 64) {
         const int p = base + lane;
         const bool valid = p <= last;
@@ -83,11 +96,14 @@ __global__ void __launch_bounds__(kHcSearchThreads) lz4_hc_search_kernel(HcArgs 
     const int b = blockIdx.x / kHcGroups;
     const int n = a.src_size[b];
     if (n < kMinLength || n > kMaxBlock) return;
-    const int p = (int)(blockIdx.x % kHcGroups) * kHcSearchThreads + (int)threadIdx.x;
-    if (p > n - kMFLimit) return;
-    gcu8 *src = (gcu8 *)a.src[b];
+    // window positions: the block's own start at hist, the window ends at wn (a workgroup past
+    // the block's last searchable position leaves here)
+    const int hist = hc_history(a, b, n), wn = hist + n;
+    const int p = hist + (int)(blockIdx.x % kHcGroups) * kHcSearchThreads + (int)threadIdx.x;
+    if (p > wn - kMFLimit) return;
+    gcu8 *src = (gcu8 *)a.src[b] - hist;
     const uint16_t *chain = a.chain + (size_t)b * kMaxBlock;
-    const int mx = min(kHcCap, n - kLastLiterals - p);   // >= 7
+    const int mx = min(kHcCap, wn - kLastLiterals - p);   // >= 7
     const uint32_t x = gload4(src + p);
     uint32_t cur = chain[p], best = 0u, best_q = 0u;
     for (int d = 0; d < a.depth && cur; d++) {
@@ -96,7 +112,7 @@ __global__ void __launch_bounds__(kHcSearchThreads) lz4_hc_search_kernel(HcArgs 
         if (gload4(src + q) != x) continue;   // a collision, or fewer than 4 bytes: depth spent
         int k = kMinMatch;
         while (k < mx) {
-            if (p + k + 16 <= n) {            // q < p: both loads end inside the block
+            if (p + k + 16 <= wn) {           // q < p: both loads end inside the window
                 const uint4 u = gload16(src + p + k), v = gload16(src + q + k);
                 const uint32_t d0 = u.x ^ v.x, d1 = u.y ^ v.y, d2 = u.z ^ v.z, d3 = u.w ^ v.w;
                 if (d0 | d1 | d2 | d3) {
@@ -105,7 +121,7 @@ __global__ void __launch_bounds__(kHcSearchThreads) lz4_hc_search_kernel(HcArgs 
                     break;
                 }
                 k += 16;
-            } else {                          // the block's last bytes, one at a time
+            } else {                          // the window's last bytes, one at a time
                 while (k < mx && src[p + k] == src[q + k]) k++;
                 break;
             }
@@ -124,14 +140,19 @@ __global__ void __launch_bounds__(kHcSearchThreads) lz4_hc_search_kernel(HcArgs 
 __global__ void __launch_bounds__(64) lz4_hc_parse_kernel(HcArgs a) {
     const int b = blockIdx.x, lane = lane_id();
     const int n = a.src_size[b], cap = a.dst_cap[b];
-    if (n < 0 || n > kMaxBlock || cap <= 0) {
-        if (lane == 0) a.result[b] = n > kMaxBlock ? kErange : 0;
+    if (n < 0 || n > kMaxBlock || cap <= 0) {   // (a slot of size -1 reads nothing more)
+        if (lane == 0) {
+            a.result[b] = n > kMaxBlock ? kErange : 0;
+            if (a.tail && n >= 0) a.tail[b] = 0;
+        }
         return;
     }
-    gcu8 *src = (gcu8 *)a.src[b];
+    // src, un and every position below are the window's: the block starts at hist
+    const int hist = hc_history(a, b, n);
+    gcu8 *src = (gcu8 *)a.src[b] - hist;
     gu8 *dst = (gu8 *)a.dst[b];
     const uint32_t *M = a.match + (size_t)b * kMaxBlock;
-    const uint32_t un = (uint32_t)n, ucap = (uint32_t)cap;
+    const uint32_t un = (uint32_t)(hist + n), ucap = (uint32_t)cap;
 
     auto put = [&](uint32_t o, uint32_t v) {   // one output byte
         if (lane == 0) dst[o] = (uint8_t)v;
@@ -147,11 +168,11 @@ __global__ void __launch_bounds__(64) lz4_hc_parse_kernel(HcArgs a) {
         if ((uint32_t)lane < len - r) dst[o + r + lane] = src[s + r + lane];
     };
 
-    uint32_t op = 0u, anchor = 0u;
+    uint32_t op = 0u, anchor = (uint32_t)hist;
     bool fail = false;
     if (n >= kMinLength) {
         const uint32_t last = un - (uint32_t)kMFLimit, end = un - (uint32_t)kLastLiterals;
-        uint32_t p = 0u;
+        uint32_t p = (uint32_t)hist;
         while (p <= last) {
             // 64 positions from p: this one's match and the next one's
             const uint32_t pos = p + (uint32_t)lane;
@@ -176,7 +197,7 @@ __global__ void __launch_bounds__(64) lz4_hc_parse_kernel(HcArgs a) {
             const uint32_t q = mm & 0xFFFFu, lim = end - sp;
             uint32_t L = mm >> 16;
             if (L == umin((uint32_t)kHcCap, lim)) {
-                // capped by the search: extend forward to at most n - 5, 8 bytes per lane
+                // capped by the search: extend forward to at most the end - 5, 8 bytes per lane
                 while (L < lim) {
                     const uint32_t o = L + 8u * (uint32_t)lane;
                     uint32_t cnt = 0u;
@@ -231,16 +252,27 @@ __global__ void __launch_bounds__(64) lz4_hc_parse_kernel(HcArgs a) {
             result = (int)(op + run);
         }
     }
-    if (lane == 0) a.result[b] = result;
+    if (lane == 0) {
+        a.result[b] = result;
+        // the large path (lz4_large.hip) stitches slices at their final literal runs: the run
+        // of a finished walk, also when it did not fit; 0 when the walk broke off
+        if (a.tail) a.tail[b] = fail ? 0 : (int)(un - anchor);
+    }
 }
 
-hipError_t launch_encode_hc(const HcArgs &a, hipStream_t s) {
+// ev (nullable): three events, recorded after the chain, the search and the parse launch
+hipError_t launch_encode_hc(const HcArgs &a, hipStream_t s, hipEvent_t *ev) {
     if (a.nblocks <= 0) return hipSuccess;
+    hipError_t e = hipSuccess;
     hipLaunchKernelGGL(lz4_hc_chain_kernel, dim3(a.nblocks), dim3(64), 0, s, a);
+    if (ev) e = hipEventRecord(ev[0], s);
     hipLaunchKernelGGL(lz4_hc_search_kernel, dim3((unsigned)a.nblocks * kHcGroups),
                        dim3(kHcSearchThreads), 0, s, a);
+    if (ev && e == hipSuccess) e = hipEventRecord(ev[1], s);
     hipLaunchKernelGGL(lz4_hc_parse_kernel, dim3(a.nblocks), dim3(64), 0, s, a);
-    return hipGetLastError();
+    if (ev && e == hipSuccess) e = hipEventRecord(ev[2], s);
+    const hipError_t le = hipGetLastError();
+    return le != hipSuccess ? le : e;
 }
 
 }  // namespace apelz4

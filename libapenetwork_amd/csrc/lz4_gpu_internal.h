@@ -215,7 +215,8 @@ hipError_t launch_cdict_prepare(const char *dict, int dict_size, int max_src, vo
 hipError_t launch_encode_exact(const BlockArgs &a, hipStream_t s);
 // The high-ratio mode (lz4_encode_hc.hip; tests/hcmodel.py restates the two constants): hash
 // chains over the block, the first `depth` chain members of every position searched for the
-// longest match, then a sequential parse with a one-step lazy rule.
+// longest match, then a sequential parse with a one-step lazy rule.  With HcArgs::prefix the
+// block is the end of a window of history + block (tests/hclargemodel.py).
 constexpr int kHcCap = 272;       // longest match the search reports (the parse extends it)
 constexpr int kHcHashBits = 14;   // chain hash; the u16 head table is 32 KiB of LDS
 constexpr int kHcMaxDepth = 256, kHcDefaultDepth = 64;
@@ -232,10 +233,15 @@ struct HcArgs {
     int nblocks, depth;
     uint16_t *chain;          // block i's at chain + i * kMaxBlock ...
     uint32_t *match;          // ... and match + i * kMaxBlock
+    const int *prefix;        // per-block bytes of history before src[i] (nullable: none); the
+                              // last min(prefix, 65536 - size) of them are used, and chain[] and
+                              // match[] are then indexed by position in history + block
+    int *tail;                // per-block length of the final literal run, as BlockArgs::tail
+                              // (nullable)
 };
 // chain build (one wave per block), search (one lane per position), parse + emit (one wave per
 // block)
-hipError_t launch_encode_hc(const HcArgs &a, hipStream_t s);
+hipError_t launch_encode_hc(const HcArgs &a, hipStream_t s, hipEvent_t *ev = nullptr);
 // compress_destSize pass 2 (lz4_destsize.hip): scratch slot i (at scratch + i*stride, encoder
 // result sres[i]) -> dst[i] cut to target[i]; src_size[i] <- consumed input
 hipError_t launch_destsize(const char *const *src, int *src_size, char *const *dst,
@@ -312,6 +318,13 @@ struct RangeArgs {
 hipError_t launch_decode_range(const RangeArgs &a, hipStream_t s);
 size_t large_scratch_layout(int nblocks, int max_src, LargeArgs *out);
 hipError_t launch_large(const LargeArgs &a, int accel, hipStream_t s, hipEvent_t *ev = nullptr);
+// The same with the high-ratio encoder on the slices: its three kernels run
+// over the slot arrays in passes of `pass` slots (1..1024) on the chain and match tables at
+// `hc` (pass * kHcSlotBytes bytes).  ev (nullable): 5 + 3 * passes events, recorded before the
+// plan, after it, after each pass's chain, search and parse, and after offsets, stitch, index.
+inline int large_hc_passes(int nslots, int pass) { return (nslots + pass - 1) / pass; }
+hipError_t launch_large_hc(const LargeArgs &a, int depth, void *hc, int pass, hipStream_t s,
+                           hipEvent_t *ev = nullptr);
 hipError_t launch_synth(char *out, size_t stride, int n, long long first, int nblocks,
                         int kind, hipStream_t s);
 

@@ -376,4 +376,53 @@ hipError_t launch_large(const LargeArgs &a, int accel, hipStream_t s, hipEvent_t
     return e;
 }
 
+// The high-ratio encoder on the slices.  Plan, offsets, stitch and index are
+// the launches above, unchanged: they need a slice's stream, its size and the length of its
+// final run, whichever encoder wrote them.  The plan's s_prefix is the history OFFERED (back to
+// the input's start or the last restart point); the high-ratio kernels use min(that, 65536 -
+// size) of it.  An absent slot has size -1: its parse wave writes result 0 and reads nothing.
+hipError_t launch_large_hc(const LargeArgs &a, int depth, void *hc, int pass, hipStream_t s,
+                           hipEvent_t *ev) {
+    if (a.nblocks <= 0) return hipSuccess;
+    int q = 0;
+    auto mark = [&]() { return ev ? hipEventRecord(ev[q++], s) : hipSuccess; };
+    hipError_t e = mark();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(large_plan_kernel, dim3((unsigned)((a.nslots + 255) / 256)), dim3(256), 0, s, a);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = mark();
+    for (int off = 0; off < a.nslots && e == hipSuccess; off += pass) {
+        HcArgs h{};
+        h.src = a.s_src + off;
+        h.src_size = a.s_size + off;
+        h.dst = a.s_dst + off;
+        h.dst_cap = a.s_cap + off;
+        h.result = a.s_res + off;
+        h.prefix = a.s_prefix + off;
+        h.tail = a.s_tail + off;
+        h.nblocks = a.nslots - off < pass ? a.nslots - off : pass;
+        h.depth = depth;
+        h.chain = (uint16_t *)hc;
+        h.match = (uint32_t *)((char *)hc + (size_t)pass * kHcChainBytes);
+        e = launch_encode_hc(h, s, ev ? ev + q : nullptr);
+        if (ev) q += 3;
+    }
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(large_offsets_kernel, dim3(a.nblocks), dim3(64), 0, s, a);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = mark();
+    if (e != hipSuccess) return e;
+    if (a.max_src > kMaxBlock) {   // (otherwise every input is one slice: nothing to stitch)
+        hipLaunchKernelGGL(large_stitch_kernel, dim3(a.nslots), dim3(256), 0, s, a);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = mark();
+    if (e == hipSuccess && a.index) {
+        hipLaunchKernelGGL(large_index_kernel, dim3(a.nblocks), dim3(64), 0, s, a);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = mark();
+    return e;
+}
+
 }  // namespace apelz4

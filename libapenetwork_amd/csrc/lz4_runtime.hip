@@ -524,16 +524,17 @@ size_t APE_LZ4_compress_hc_scratch_size(int nblocks) {
     return (size_t)(nblocks < kHcSub ? nblocks : kHcSub) * kHcSlotBytes;
 }
 
-int APE_LZ4_compress_hc_batch_dev(const char *const *d_src, const int *d_srcSize,
-                                  char *const *d_dst, const int *d_dstCap, int *d_result,
-                                  int nblocks, int depth, void *d_scratch, size_t scratch_bytes,
-                                  void *stream) {
+namespace {
+// d_prefixSize (nullable): per-block bytes of history before d_src[i]
+int hc_batch(const char *what, const char *const *d_src, const int *d_srcSize,
+             const int *d_prefixSize, char *const *d_dst, const int *d_dstCap, int *d_result,
+             int nblocks, int depth, void *d_scratch, size_t scratch_bytes, void *stream) {
     if (nblocks < 0 || depth < 0 || depth > kHcMaxDepth || !d_scratch ||
         ((uintptr_t)d_scratch & 15u) || scratch_bytes < kHcSlotBytes ||
         (nblocks > 0 && (!d_src || !d_srcSize || !d_dst || !d_dstCap || !d_result))) {
-        snprintf(g_err, sizeof g_err, "compress_hc: nblocks %d, depth %d (0..%d), scratch of %zu "
-                 "bytes at %p (need %zu bytes, 16-byte aligned)", nblocks, depth, kHcMaxDepth,
-                 scratch_bytes, d_scratch, kHcSlotBytes);
+        snprintf(g_err, sizeof g_err, "%s: nblocks %d, depth %d (0..%d), scratch of %zu "
+                 "bytes at %p (need %zu bytes, 16-byte aligned)", what, nblocks, depth,
+                 kHcMaxDepth, scratch_bytes, d_scratch, kHcSlotBytes);
         return APE_LZ4_GPU_EINVAL;
     }
     int rc = check_device();
@@ -550,6 +551,7 @@ int APE_LZ4_compress_hc_batch_dev(const char *const *d_src, const int *d_srcSize
         a.dst = d_dst + off;
         a.dst_cap = d_dstCap + off;
         a.result = d_result + off;
+        a.prefix = d_prefixSize ? d_prefixSize + off : nullptr;
         a.nblocks = nblocks - off < sub ? nblocks - off : sub;
         a.depth = depth ? depth : kHcDefaultDepth;
         a.chain = (uint16_t *)d_scratch;
@@ -557,6 +559,24 @@ int APE_LZ4_compress_hc_batch_dev(const char *const *d_src, const int *d_srcSize
         e = launch_encode_hc(a, (hipStream_t)stream);
     }
     return finish_launch(e, "lz4_hc_chain_kernel + lz4_hc_search_kernel + lz4_hc_parse_kernel");
+}
+}  // namespace
+
+int APE_LZ4_compress_hc_batch_dev(const char *const *d_src, const int *d_srcSize,
+                                  char *const *d_dst, const int *d_dstCap, int *d_result,
+                                  int nblocks, int depth, void *d_scratch, size_t scratch_bytes,
+                                  void *stream) {
+    return hc_batch("compress_hc", d_src, d_srcSize, nullptr, d_dst, d_dstCap, d_result, nblocks,
+                    depth, d_scratch, scratch_bytes, stream);
+}
+
+int APE_LZ4_compress_hc_withPrefix_batch_dev(const char *const *d_src, const int *d_srcSize,
+                                             const int *d_prefixSize, char *const *d_dst,
+                                             const int *d_dstCap, int *d_result, int nblocks,
+                                             int depth, void *d_scratch, size_t scratch_bytes,
+                                             void *stream) {
+    return hc_batch("compress_hc_withPrefix", d_src, d_srcSize, d_prefixSize, d_dst, d_dstCap,
+                    d_result, nblocks, depth, d_scratch, scratch_bytes, stream);
 }
 
 // ---- inputs of any size as one block (lz4_large.hip) ----
@@ -780,6 +800,144 @@ int large_batch(const char *const *d_src, const int *d_srcSize, char *const *d_d
                          "large plan + lz4_encode_kernel + offsets + stitch");
 }
 }  // namespace
+
+// ---- the high-ratio mode on inputs of any size (lz4_large.hip launch_large_hc) ----
+// Scratch: the large path's layout, then the chain and match tables of one pass of slices.
+namespace {
+size_t up16z(size_t x) { return (x + 15) & ~(size_t)15; }
+
+// slices per pass out of `want` (0 = all): 1 .. min(slots, kHcSub)
+int large_hc_pass(long long nslots, long long want) {
+    long long most = nslots < kHcSub ? nslots : kHcSub;
+    if (most < 1) most = 1;
+    if (want <= 0 || want > most) want = most;
+    return (int)want;
+}
+
+int large_hc_batch(const char *const *d_src, const int *d_srcSize, char *const *d_dst,
+                   const int *d_dstCap, int *d_result, int nblocks, int maxSrcSize, int depth,
+                   void *d_scratch, size_t scratch_bytes, int restartBytes, void *d_index,
+                   size_t index_stride, void *stream, float *ms6) {
+    if (nblocks < 0 || (nblocks > 0 && (!d_src || !d_srcSize || !d_dst || !d_dstCap ||
+                                         !d_result || !d_scratch))) {
+        snprintf(g_err, sizeof g_err, "compress_large_hc: invalid argument (a null array or a "
+                 "negative count)");
+        return APE_LZ4_GPU_EINVAL;
+    }
+    if (depth < 0 || depth > kHcMaxDepth) {
+        snprintf(g_err, sizeof g_err, "compress_large_hc: depth %d outside 0..%d", depth,
+                 kHcMaxDepth);
+        return APE_LZ4_GPU_EINVAL;
+    }
+    if (maxSrcSize < 1 || maxSrcSize > kLargeMaxSrc) {
+        snprintf(g_err, sizeof g_err, "compress_large_hc: maxSrcSize %d outside [1, %d]",
+                 maxSrcSize, kLargeMaxSrc);
+        return APE_LZ4_GPU_EINVAL;
+    }
+    if (!restart_ok(restartBytes)) {
+        snprintf(g_err, sizeof g_err, "compress_large_hc: restartBytes %d is neither 0 nor a "
+                 "positive multiple of the slice size %d", restartBytes, large_slice_size());
+        return APE_LZ4_GPU_EINVAL;
+    }
+    if (d_index && (((uintptr_t)d_index & 15u) || index_stride % 16u ||
+                    index_stride < large_index_size(maxSrcSize, restartBytes))) {
+        snprintf(g_err, sizeof g_err, "compress_large_hc: index at %p with stride %zu, need "
+                 "16-byte alignment and a stride that is a multiple of 16 and >= %zu", d_index,
+                 index_stride, large_index_size(maxSrcSize, restartBytes));
+        return APE_LZ4_GPU_EINVAL;
+    }
+    size_t base = 0;
+    LargeArgs a{};
+    if (nblocks > 0) {
+        a.restart = restartBytes;
+        a.index = (char *)d_index;
+        a.index_stride = index_stride;
+        a.src = d_src;
+        a.src_size = d_srcSize;
+        a.dst = d_dst;
+        a.dst_cap = d_dstCap;
+        a.result = d_result;
+        a.nblocks = nblocks;
+        a.max_src = maxSrcSize;
+        a.buf = (char *)d_scratch;
+        base = up16z(large_scratch_layout(nblocks, maxSrcSize, &a));
+        if (base == 0) {
+            snprintf(g_err, sizeof g_err, "compress_large_hc: %d inputs of up to %d bytes are "
+                     "more slices than one call takes; split the batch", nblocks, maxSrcSize);
+            return APE_LZ4_GPU_EINVAL;
+        }
+        if (scratch_bytes < base + kHcSlotBytes || ((uintptr_t)d_scratch & 15u)) {
+            snprintf(g_err, sizeof g_err, "compress_large_hc: scratch of %zu bytes at %p, need "
+                     "%zu bytes 16-byte aligned", scratch_bytes, d_scratch, base + kHcSlotBytes);
+            return APE_LZ4_GPU_EINVAL;
+        }
+    }
+    int rc = check_device();
+    if (rc) return rc;
+    if (nblocks == 0) return APE_LZ4_GPU_OK;
+    // as many slices per pass as the caller's scratch holds
+    const int pass = large_hc_pass(a.nslots, (long long)((scratch_bytes - base) / kHcSlotBytes));
+    const char *what = "large plan + lz4_hc kernels + offsets + stitch";
+    const hipStream_t s = (hipStream_t)stream;
+    const int d = depth ? depth : kHcDefaultDepth;
+    if (!ms6) return finish_launch(launch_large_hc(a, d, (char *)d_scratch + base, pass, s), what);
+    // the timed form: events around every launch, the passes' times summed per kernel
+    const int passes = large_hc_passes(a.nslots, pass), nev = 5 + 3 * passes;
+    std::vector<hipEvent_t> ev((size_t)nev, nullptr);
+    hipError_t e = hipSuccess;
+    for (int q = 0; q < nev && e == hipSuccess; q++) e = hipEventCreate(&ev[q]);
+    rc = e == hipSuccess ? APE_LZ4_GPU_OK : finish_launch(e, "hipEventCreate");
+    if (rc == APE_LZ4_GPU_OK)
+        rc = finish_launch(launch_large_hc(a, d, (char *)d_scratch + base, pass, s, ev.data()), what);
+    for (int q = 0; q < 6; q++) ms6[q] = 0.f;
+    if (rc == APE_LZ4_GPU_OK) {
+        e = hipEventSynchronize(ev[nev - 1]);
+        auto span = [&](int slot, int from) {
+            float ms = 0.f;
+            if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[from], ev[from + 1]);
+            ms6[slot] += ms;
+        };
+        span(0, 0);
+        for (int p = 0; p < passes; p++)
+            for (int k = 0; k < 3; k++) span(1 + k, 1 + 3 * p + k);
+        span(4, 1 + 3 * passes);
+        span(5, 2 + 3 * passes);   // (the index launch, after it, is not in any figure)
+        rc = finish_launch(e, "compress_large_hc stage events");
+    }
+    for (int q = 0; q < nev; q++)
+        if (ev[q]) (void)hipEventDestroy(ev[q]);
+    return rc;
+}
+}  // namespace
+
+size_t APE_LZ4_compress_large_hc_scratch_size(int nblocks, int maxSrcSize, int passSlices) {
+    if (nblocks < 0 || maxSrcSize < 1 || maxSrcSize > kLargeMaxSrc || passSlices < 0) return 0;
+    const size_t base = large_scratch_layout(nblocks, maxSrcSize, nullptr);
+    if (!base) return (size_t)-1;   // more slice slots than one call takes: split the batch
+    const long long S = large_slice_size();
+    const long long nsl = maxSrcSize <= kMaxBlock ? 1 : ((long long)maxSrcSize + S - 1) / S;
+    return up16z(base) + (size_t)large_hc_pass(nblocks * nsl, passSlices) * kHcSlotBytes;
+}
+
+int APE_LZ4_compress_large_hc_batch_dev(const char *const *d_src, const int *d_srcSize,
+                                        char *const *d_dst, const int *d_dstCap, int *d_result,
+                                        int nblocks, int maxSrcSize, int depth, void *d_scratch,
+                                        size_t scratch_bytes, int restartBytes, void *d_index,
+                                        size_t index_stride, void *stream) {
+    return large_hc_batch(d_src, d_srcSize, d_dst, d_dstCap, d_result, nblocks, maxSrcSize, depth,
+                          d_scratch, scratch_bytes, restartBytes, d_index, index_stride, stream,
+                          nullptr);
+}
+
+int APE_LZ4_compress_large_hc_timed_dev(const char *const *d_src, const int *d_srcSize,
+                                        char *const *d_dst, const int *d_dstCap, int *d_result,
+                                        int nblocks, int maxSrcSize, int depth, void *d_scratch,
+                                        size_t scratch_bytes, int restartBytes, void *stream,
+                                        float *ms6) {
+    if (!ms6) return APE_LZ4_GPU_EINVAL;
+    return large_hc_batch(d_src, d_srcSize, d_dst, d_dstCap, d_result, nblocks, maxSrcSize, depth,
+                          d_scratch, scratch_bytes, restartBytes, nullptr, 0, stream, ms6);
+}
 
 int APE_LZ4_compress_batch_strided_dev(const char *d_src, size_t src_stride, const int *d_srcSize,
                                        char *d_dst, size_t dst_stride, const int *d_dstCap,
