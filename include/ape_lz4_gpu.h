@@ -255,6 +255,61 @@ int APE_LZ4_compress_hc_withPrefix_batch_dev(const char *const *d_src, const int
                                              int depth, void *d_scratch, size_t scratch_bytes,
                                              void *stream);
 
+/* ---- the high-ratio mode against a prepared dictionary (lz4_hc_cdict.hip) ----
+ * Many independent messages, one shared dictionary, the deep search: message i is compressed
+ * with the dictionary's tail as its history, without a per-message copy of the dictionary and
+ * without a per-message chain build over it.  A PREPARED HIGH-RATIO DICTIONARY is a device
+ * object of its own kind (not the fast encoder's, above): a padded copy of the dictionary's
+ * tail, and the hash chains and the head table of that tail as the chain build leaves them.
+ *
+ * hc_cdict_size    : bytes of device memory one such object takes (a compile-time constant, a
+ *   multiple of 16).
+ * hc_cdict_window  : bytes D of the dictionary's tail the object uses: D = min(dictSize,
+ *   65536 - maxSrcSize), NOT rounded to a multiple of 64 (the rule of compress_hc_withPrefix,
+ *   not of cdict_window); 0 is legal.  Host-only arithmetic; -1 for arguments out of range.
+ * hc_cdict_prepare : d_dict[dictSize - D, dictSize) -> the object at d_cdict (16-byte aligned,
+ *   cdict_bytes >= hc_cdict_size()).  maxSrcSize (1..65536) trades dictionary for message size.
+ *   dictSize may exceed 65536 (only the tail counts); dictSize 0 (d_dict may then be NULL) is
+ *   legal.  One asynchronous launch, no allocation, no sync, graph-capturable.  It writes EVERY
+ *   byte of d_cdict[0, hc_cdict_size()), so two prepares of the same input give identical bytes.
+ * compress_hc_usingCDict : d_result[i] <- size of one valid LZ4 block of d_src[i][0,
+ *   d_srcSize[i]) that decompress_safe_usingDict decodes with the CALLER'S ORIGINAL dictionary
+ *   (any size, any placement).  THE BYTES are exactly those APE_LZ4_compress_hc_withPrefix_
+ *   batch_dev writes for the staged window [dictionary's last D bytes | message] with prefix D:
+ *   a pure function of (message, those D bytes, depth), tests/hcdictmodel.py on the CPU.  So,
+ *   unlike compress_usingCDict, a match that starts in the dictionary runs on into the message,
+ *   and the three positions before the message are chain members; a message shorter than 13
+ *   bytes is one literal run.  With D = 0 the bytes are APE_LZ4_compress_hc_batch_dev's.
+ *   maxSrcSize is the host-side bound that sizes the grid and the scratch; the kernels compare
+ *   it with the object's header BEFORE anything else of the object is used, and a mismatch, a
+ *   wrong magic (the fast encoder's object, say) or an object that was never prepared gives
+ *   EVERY block of the call result 0.  depth is 0..256, 0 meaning 64.  Per block: 0 for a
+ *   negative size or a block that does not fit d_dstCap[i] (checked before each sequence is
+ *   written), APE_LZ4_GPU_ERANGE above maxSrcSize; the other blocks are unaffected.  Nothing
+ *   outside d_src[i][0, size), the object and d_dst[i][0, cap) is touched.  The object is only
+ *   read: any number of calls, on any streams, may share it.
+ * scratch : the caller's, 16-byte aligned.  scratch_size(nblocks, maxSrcSize) is what one pass
+ *   takes: per message a u16 chain entry for each window position from D - 3 on (maxSrcSize +
+ *   3 of them) and a u32 match record per message position, each rounded to 16 bytes -- about
+ *   6 x maxSrcSize bytes -- for at most 262144 / ceil(maxSrcSize / 256) messages at a time; 0
+ *   for nblocks <= 0 or maxSrcSize out of range.  A smaller scratch, at least scratch_size(1,
+ *   maxSrcSize), makes the call run several passes (their number decided on the host) with
+ *   identical bytes.  Every scratch byte the call reads it has written before, in the same
+ *   call.  No allocation, no sync: three stream-ordered launches per pass, graph-capturable.
+ * APE_LZ4_GPU_EINVAL before any device call for a null array (nblocks > 0), nblocks < 0,
+ * dictSize < 0, depth or maxSrcSize out of range, a null, misaligned or too small object
+ * (prepare; compress cannot see its size) or scratch; 0 otherwise. */
+size_t APE_LZ4_hc_cdict_size(void);
+int APE_LZ4_hc_cdict_window(int dictSize, int maxSrcSize);
+int APE_LZ4_hc_cdict_prepare_dev(const char *d_dict, int dictSize, int maxSrcSize, void *d_cdict,
+                                 size_t cdict_bytes, void *stream);
+size_t APE_LZ4_compress_hc_usingCDict_scratch_size(int nblocks, int maxSrcSize);
+int APE_LZ4_compress_hc_usingCDict_batch_dev(const char *const *d_src, const int *d_srcSize,
+                                             char *const *d_dst, const int *d_dstCap,
+                                             int *d_result, int nblocks, const void *d_cdict,
+                                             int maxSrcSize, int depth, void *d_scratch,
+                                             size_t scratch_bytes, void *stream);
+
 /* ---- inputs larger than one encoder block, as ONE LZ4 block (lz4_large.hip) ----
  * == N x APE_LZ4_compress_fast on inputs of any size up to maxSrcSize: d_result[i] <-
  * size of ONE valid LZ4 block of d_src[i][0, d_srcSize[i]) (decodes with decompress_safe,

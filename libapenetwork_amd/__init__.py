@@ -101,6 +101,11 @@ def lib():
             "APE_LZ4_compress_hc_scratch_size": (sz, [i]),
             "APE_LZ4_compress_hc_batch_dev": (i, [p, p, p, p, p, i, i, p, sz, p]),
             "APE_LZ4_compress_hc_withPrefix_batch_dev": (i, [p, p, p, p, p, p, i, i, p, sz, p]),
+            "APE_LZ4_hc_cdict_size": (sz, []),
+            "APE_LZ4_hc_cdict_window": (i, [i, i]),
+            "APE_LZ4_hc_cdict_prepare_dev": (i, [p, i, i, p, sz, p]),
+            "APE_LZ4_compress_hc_usingCDict_scratch_size": (sz, [i, i]),
+            "APE_LZ4_compress_hc_usingCDict_batch_dev": (i, [p, p, p, p, p, i, p, i, i, p, sz, p]),
             "APE_LZ4_compress_large_hc_scratch_size": (sz, [i, i, i]),
             "APE_LZ4_compress_large_hc_batch_dev": (i, [p, p, p, p, p, i, i, i, p, sz, i, p, sz, p]),
             "APE_LZ4_compress_large_hc_timed_dev": (i, [p, p, p, p, p, i, i, i, p, sz, i, p, p]),
@@ -625,6 +630,59 @@ def compress_hc_prefix_ptr_batch(src_ptrs, src_sizes, prefix_sizes, dst_ptrs, ca
         _ptr(src_ptrs), _ptr(src_sizes), _ptr(prefix_sizes), _ptr(dst_ptrs), _ptr(caps),
         _ptr(results), n, depth, _ptr(scratch), scratch.numel(), _stream(stream)),
         "APE_LZ4_compress_hc_withPrefix_batch_dev")
+
+
+def hc_cdict_size():
+    """APE_LZ4_hc_cdict_size: bytes of device memory one prepared high-ratio dictionary takes."""
+    return lib().APE_LZ4_hc_cdict_size()
+
+
+def hc_cdict_window(dict_size, max_src_size):
+    """APE_LZ4_hc_cdict_window: bytes of the dictionary's tail such an object uses (not rounded)."""
+    return lib().APE_LZ4_hc_cdict_window(dict_size, max_src_size)
+
+
+def hc_cdict_prepare(dict_tensor, max_src_size, cdict_tensor, stream=None):
+    """APE_LZ4_hc_cdict_prepare_dev: dict_tensor (uint8 CUDA, any placement; may be empty) ->
+    the prepared high-ratio dictionary in cdict_tensor (uint8 CUDA, >= hc_cdict_size() bytes,
+    16-byte aligned) for messages of up to max_src_size bytes.  Returns cdict_tensor."""
+    import torch
+    _arr(dict_tensor, "hc_cdict_prepare dict", torch.uint8)
+    _arr(cdict_tensor, "hc_cdict_prepare cdict", torch.uint8)
+    _check(lib().APE_LZ4_hc_cdict_prepare_dev(
+        _ptr(dict_tensor) if dict_tensor.numel() else None, dict_tensor.numel(), max_src_size,
+        _ptr(cdict_tensor), cdict_tensor.numel(), _stream(stream)),
+        "APE_LZ4_hc_cdict_prepare_dev")
+    return cdict_tensor
+
+
+def compress_hc_cdict_scratch_size(nblocks, max_src_size):
+    """APE_LZ4_compress_hc_usingCDict_scratch_size: scratch bytes for one pass over nblocks."""
+    return lib().APE_LZ4_compress_hc_usingCDict_scratch_size(nblocks, max_src_size)
+
+
+def compress_hc_cdict_batch(src_ptrs, src_sizes, dst_ptrs, caps, results, cdict, max_src_size,
+                            depth, scratch, stream=None):
+    """The high-ratio mode against one prepared high-ratio dictionary (hc_cdict_prepare with the
+    same max_src_size); pointer-array form (int64 tensors of pointers).  depth as
+    compress_hc_ptr_batch; scratch is a uint8 CUDA tensor of at least
+    compress_hc_cdict_scratch_size(1, max_src_size) bytes (fewer than ..._scratch_size(N, ...):
+    several passes, same bytes).  Each block decodes with decompress_dict_batch given the
+    original dictionary.  Allocates nothing, so it can be graph-captured."""
+    import torch
+    what = "compress_hc_cdict_batch"
+    _arr(src_sizes, what + " src_sizes", torch.int32)
+    n = src_sizes.shape[0]
+    _ptr_args(what, n, src_ptrs=(src_ptrs, _i64()), src_sizes=(src_sizes, _i32()),
+              dst_ptrs=(dst_ptrs, _i64()), caps=(caps, _i32()), results=(results, _i32()))
+    _arr(cdict, what + " cdict", torch.uint8)
+    if cdict.numel() < hc_cdict_size():
+        raise ValueError(what + " cdict: smaller than hc_cdict_size()")
+    _arr(scratch, what + " scratch", torch.uint8)
+    _check(lib().APE_LZ4_compress_hc_usingCDict_batch_dev(
+        _ptr(src_ptrs), _ptr(src_sizes), _ptr(dst_ptrs), _ptr(caps), _ptr(results), n,
+        _ptr(cdict), max_src_size, depth, _ptr(scratch), scratch.numel(), _stream(stream)),
+        "APE_LZ4_compress_hc_usingCDict_batch_dev")
 
 
 def compress_large_hc_scratch_size(nblocks, max_src_size, pass_slices=0):

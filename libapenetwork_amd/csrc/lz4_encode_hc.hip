@@ -21,19 +21,8 @@
 namespace apelz4 {
 namespace {
 
-constexpr int kHcTable = 1 << kHcHashBits;
 constexpr int kHcSearchThreads = 256;
 constexpr int kHcGroups = kMaxBlock / kHcSearchThreads;   // search workgroups per block
-
-__device__ __forceinline__ uint32_t hc_hash(uint32_t x) {
-    return (x * 2654435761u) >> (32 - kHcHashBits);
-}
-
-// bytes of a length field after the token (value v >= 15: 255s, then the remainder)
-__device__ __forceinline__ uint32_t len_bytes(uint32_t v) { return v >= 15u ? (v - 15u) / 255u + 1u : 0u; }
-
-// leading equal bytes of two little-endian words whose xor is x (x != 0)
-__device__ __forceinline__ uint32_t first_diff(uint32_t x) { return (uint32_t)__builtin_ctz(x) >> 3; }
 
 // bytes of history block b (of 0 <= n <= kMaxBlock bytes) uses: what the caller offers, as far
 // as one window of u16 positions holds it; not rounded, a negative prefix counts as none

@@ -220,6 +220,14 @@ hipError_t launch_encode_exact(const BlockArgs &a, hipStream_t s);
 constexpr int kHcCap = 272;       // longest match the search reports (the parse extends it)
 constexpr int kHcHashBits = 14;   // chain hash; the u16 head table is 32 KiB of LDS
 constexpr int kHcMaxDepth = 256, kHcDefaultDepth = 64;
+constexpr int kHcTable = 1 << kHcHashBits;
+__device__ __forceinline__ uint32_t hc_hash(uint32_t x) {
+    return (x * 2654435761u) >> (32 - kHcHashBits);
+}
+// bytes of a length field after the token (value v >= 15: 255s, then the remainder)
+__device__ __forceinline__ uint32_t len_bytes(uint32_t v) { return v >= 15u ? (v - 15u) / 255u + 1u : 0u; }
+// leading equal bytes of two little-endian words whose xor is x (x != 0)
+__device__ __forceinline__ uint32_t first_diff(uint32_t x) { return (uint32_t)__builtin_ctz(x) >> 3; }
 // scratch of one block: chain[p] (u16: nearest earlier position with p's hash, + 1; 0 = none)
 // and match[p] (u32: length << 16 | source; 0 = none) for every position
 constexpr size_t kHcChainBytes = (size_t)kMaxBlock * sizeof(uint16_t);
@@ -242,6 +250,58 @@ struct HcArgs {
 // chain build (one wave per block), search (one lane per position), parse + emit (one wave per
 // block)
 hipError_t launch_encode_hc(const HcArgs &a, hipStream_t s, hipEvent_t *ev = nullptr);
+
+// ---- prepared high-ratio dictionary (lz4_hc_cdict.hip) ----
+// The window of message m is [the dictionary's last D bytes | m], D = min(dictSize, 65536 -
+// maxSrcSize), not rounded; the bytes are compress_hc_withPrefix's for that window
+// (tests/hcdictmodel.py).  One device object, every region 16-byte aligned:
+//   [0, 16)              header: magic, D, maxSrcSize, 0
+//   [kHdHead, kHdChain)  the u16 head table (position + 1, 0 = empty) as the chain build leaves
+//                        it after window positions 0 .. D - 4, the ones whose 4 bytes lie in
+//                        the dictionary
+//   [kHdChain, kHdWin)   chain[0 .. D - 4] of those positions (u16), zero up to entry 65535
+//   [kHdWin, kHdSize)    kCdFront bytes of pad, the window's D dictionary bytes, then zero to
+//                        the object's end (>= kCdBack bytes): a 16-byte load at any of the D
+//                        positions stays inside
+constexpr uint32_t kHdMagic = 0x44485A4Cu;   // "LZHD"
+constexpr uint32_t kHdHead = 16u, kHdChain = kHdHead + 2u * (1u << kHcHashBits);
+constexpr uint32_t kHdWin = kHdChain + 2u * (uint32_t)kMaxBlock;
+constexpr uint32_t kHdSize = kHdWin + kCdFront + (uint32_t)kMaxBlock + kCdBack;
+static_assert(kHdChain % 16u == 0u && kHdWin % 16u == 0u && kHdSize % 16u == 0u,
+              "prepared high-ratio dictionary regions");
+// D of a prepared high-ratio dictionary (host and device; 1 <= max_src <= 65536)
+__host__ __device__ inline int hc_cdict_window(int dict_size, int max_src) {
+    const int room = kMaxBlock - max_src;
+    return dict_size < room ? dict_size : room;
+}
+// scratch of one message: chain[] of the window positions from D - 3 on (entry w - D + 3) and
+// one match record per message position
+inline size_t hc_cdict_chain_entries(int max_src) { return ((size_t)max_src + 3 + 7) & ~(size_t)7; }
+inline size_t hc_cdict_match_entries(int max_src) { return ((size_t)max_src + 3) & ~(size_t)3; }
+inline size_t hc_cdict_slot_bytes(int max_src) {
+    return hc_cdict_chain_entries(max_src) * sizeof(uint16_t) +
+           hc_cdict_match_entries(max_src) * sizeof(uint32_t);
+}
+constexpr int kHcdThreads = 256;   // search lanes per workgroup
+inline int hc_cdict_groups(int max_src) { return (max_src + kHcdThreads - 1) / kHcdThreads; }
+struct HcDictArgs {
+    const char *const *src;   // caller's arrays, one entry per message of this pass
+    const int *src_size;
+    char *const *dst;
+    const int *dst_cap;
+    int *result;
+    int nblocks, depth;
+    int max_src;              // the caller's bound; the kernels compare it with the header's
+    const uint8_t *cdict;
+    uint16_t *chain;          // message i's at chain + i * chain_stride ...
+    uint32_t *match;          // ... and match + i * match_stride (entries)
+    uint32_t chain_stride, match_stride;
+};
+hipError_t launch_hc_cdict_prepare(const char *dict, int dict_size, int max_src, void *cdict,
+                                   hipStream_t s);
+// chain build (one wave per message), search (one lane per message position), parse + emit
+// (one wave per message)
+hipError_t launch_encode_hc_cdict(const HcDictArgs &a, hipStream_t s);
 // compress_destSize pass 2 (lz4_destsize.hip): scratch slot i (at scratch + i*stride, encoder
 // result sres[i]) -> dst[i] cut to target[i]; src_size[i] <- consumed input
 hipError_t launch_destsize(const char *const *src, int *src_size, char *const *dst,

@@ -579,6 +579,89 @@ int APE_LZ4_compress_hc_withPrefix_batch_dev(const char *const *d_src, const int
                     d_result, nblocks, depth, d_scratch, scratch_bytes, stream);
 }
 
+// ---- the high-ratio mode against a prepared dictionary (lz4_hc_cdict.hip) ----
+size_t APE_LZ4_hc_cdict_size(void) { return (size_t)kHdSize; }
+
+int APE_LZ4_hc_cdict_window(int dictSize, int maxSrcSize) {
+    if (dictSize < 0 || maxSrcSize < 1 || maxSrcSize > kMaxBlock) return -1;
+    return hc_cdict_window(dictSize, maxSrcSize);
+}
+
+int APE_LZ4_hc_cdict_prepare_dev(const char *d_dict, int dictSize, int maxSrcSize, void *d_cdict,
+                                 size_t cdict_bytes, void *stream) {
+    if (dictSize < 0 || (dictSize > 0 && !d_dict) || maxSrcSize < 1 || maxSrcSize > kMaxBlock ||
+        !d_cdict || cdict_bytes < (size_t)kHdSize || ((uintptr_t)d_cdict & 15u)) {
+        snprintf(g_err, sizeof g_err, "hc_cdict_prepare: dictSize %d, maxSrcSize %d (1..%d), "
+                 "object of %zu bytes at %p (need %u bytes, 16-byte aligned)", dictSize,
+                 maxSrcSize, kMaxBlock, cdict_bytes, d_cdict, kHdSize);
+        return APE_LZ4_GPU_EINVAL;
+    }
+    int rc = check_device();
+    if (rc) return rc;
+    return finish_launch(launch_hc_cdict_prepare(d_dict, dictSize, maxSrcSize, d_cdict,
+                                                 (hipStream_t)stream),
+                         "lz4_hc_cdict_prepare_kernel");
+}
+
+namespace {
+// messages per scratch pass: as many as make kHcSub x 256 search workgroups
+inline int hc_cdict_sub(int maxSrcSize) {
+    return kHcSub * (kMaxBlock / kHcdThreads) / hc_cdict_groups(maxSrcSize);
+}
+}  // namespace
+
+size_t APE_LZ4_compress_hc_usingCDict_scratch_size(int nblocks, int maxSrcSize) {
+    if (nblocks <= 0 || maxSrcSize < 1 || maxSrcSize > kMaxBlock) return 0;
+    const int sub = hc_cdict_sub(maxSrcSize);
+    return (size_t)(nblocks < sub ? nblocks : sub) * hc_cdict_slot_bytes(maxSrcSize);
+}
+
+int APE_LZ4_compress_hc_usingCDict_batch_dev(const char *const *d_src, const int *d_srcSize,
+                                             char *const *d_dst, const int *d_dstCap,
+                                             int *d_result, int nblocks, const void *d_cdict,
+                                             int maxSrcSize, int depth, void *d_scratch,
+                                             size_t scratch_bytes, void *stream) {
+    const bool range = maxSrcSize >= 1 && maxSrcSize <= kMaxBlock;
+    const size_t slot = range ? hc_cdict_slot_bytes(maxSrcSize) : 0;
+    if (nblocks < 0 || !range || depth < 0 || depth > kHcMaxDepth || !d_cdict ||
+        ((uintptr_t)d_cdict & 15u) || !d_scratch || ((uintptr_t)d_scratch & 15u) ||
+        scratch_bytes < slot ||
+        (nblocks > 0 && (!d_src || !d_srcSize || !d_dst || !d_dstCap || !d_result))) {
+        snprintf(g_err, sizeof g_err, "compress_hc_usingCDict: nblocks %d, maxSrcSize %d (1..%d), "
+                 "depth %d (0..%d), object at %p, scratch of %zu bytes at %p (need %zu bytes; "
+                 "both 16-byte aligned)", nblocks, maxSrcSize, kMaxBlock, depth, kHcMaxDepth,
+                 d_cdict, scratch_bytes, d_scratch, slot);
+        return APE_LZ4_GPU_EINVAL;
+    }
+    int rc = check_device();
+    if (rc) return rc;
+    // as many messages per pass as the caller's scratch holds
+    const size_t fit = scratch_bytes / slot;
+    int sub = hc_cdict_sub(maxSrcSize);
+    if (fit < (size_t)sub) sub = (int)fit;
+    if (sub > nblocks) sub = nblocks;
+    hipError_t e = hipSuccess;
+    for (int off = 0; off < nblocks && e == hipSuccess; off += sub) {
+        HcDictArgs a{};
+        a.src = d_src + off;
+        a.src_size = d_srcSize + off;
+        a.dst = d_dst + off;
+        a.dst_cap = d_dstCap + off;
+        a.result = d_result + off;
+        a.nblocks = nblocks - off < sub ? nblocks - off : sub;
+        a.depth = depth ? depth : kHcDefaultDepth;
+        a.max_src = maxSrcSize;
+        a.cdict = (const uint8_t *)d_cdict;
+        a.chain_stride = (uint32_t)hc_cdict_chain_entries(maxSrcSize);
+        a.match_stride = (uint32_t)hc_cdict_match_entries(maxSrcSize);
+        a.chain = (uint16_t *)d_scratch;
+        a.match = (uint32_t *)((char *)d_scratch + (size_t)sub * a.chain_stride * sizeof(uint16_t));
+        e = launch_encode_hc_cdict(a, (hipStream_t)stream);
+    }
+    return finish_launch(e, "lz4_hc_cdict_chain_kernel + lz4_hc_cdict_search_kernel + "
+                            "lz4_hc_cdict_parse_kernel");
+}
+
 // ---- inputs of any size as one block (lz4_large.hip) ----
 namespace {
 constexpr int kLargeMaxSrc = 0x7E000000;   // LZ4_MAX_INPUT_SIZE (ref src/ape_lz4.h)
