@@ -11,7 +11,11 @@ APE_LZ4_GPU_ERANGE; otherwise 0 <= ret <= cap, a capacity >= compressBound never
 nonzero block decodes with the oracle's decompress_safe_usingDict and the ORIGINAL dictionary
 to the message.  Canaries around every dst slot are checked per batch.
 
-  python3 tests/fuzz/gpu_cdict_fuzz.py SECONDS [SEED]
+With --model K the bytes of every K-th block are also compared with tests/encmodel.py's
+encode_cdict (the definition of this encoder's output; the pytest suite holds the kernel to it in
+tests/test_gpu_cdict_model.py).
+
+  python3 tests/fuzz/gpu_cdict_fuzz.py SECONDS [SEED] [--model K]
 prints a JSON summary; exit 1 on the first mismatch."""
 import ctypes
 import json
@@ -64,15 +68,22 @@ def fail(what, **kw):
 
 
 def main():
-    seconds = float(sys.argv[1]) if len(sys.argv) > 1 else 60.0
-    seed = int(sys.argv[2]) if len(sys.argv) > 2 else 20261
+    argv = sys.argv[1:]
+    model_every = 0
+    if "--model" in argv:
+        at = argv.index("--model")
+        model_every = int(argv[at + 1])
+        del argv[at:at + 2]
+        import encmodel
+    seconds = float(argv[0]) if len(argv) > 0 else 60.0
+    seed = int(argv[1]) if len(argv) > 1 else 20261
     import torch
     import libapenetwork_amd as amd
     if not torch.cuda.is_available():
         sys.exit("no GPU")
     orc = ctypes.CDLL(os.path.join(os.path.dirname(TESTS), "oracle", "liblz4_oracle.so"))
     rng = random.Random(seed)
-    t0, nb, checked, erange = time.time(), 0, 0, 0
+    t0, nb, checked, erange, modelled = time.time(), 0, 0, 0, 0
     while time.time() - t0 < seconds:
         dsz = rng.choice([0, 1, 63, 64, 100, 4096, 32768, 61440, 65536, 70000, rng.randrange(70001)])
         max_src = rng.choice([1, 64, 128, 1024, 4096, 8192, 65536, rng.randrange(1, 65537)])
@@ -106,6 +117,12 @@ def main():
                 continue
             if r < 0 or r > cap:
                 fail("range", **info)
+            if model_every and i % model_every == 0:
+                want = encmodel.encode_cdict(m, d, max_src)
+                out = fetch(dst, doffs[i], r)
+                if (r, out) != ((len(want), want) if len(want) <= cap else (0, b"")):
+                    fail("model", model=len(want), **info)
+                modelled += 1
             if r == 0:
                 if cap >= amd.compressBound(len(m)):
                     fail("failed at the bound", **info)
@@ -120,7 +137,8 @@ def main():
         checked += len(msgs)
         nb += 1
     print(json.dumps({"seconds": round(time.time() - t0, 1), "seed": seed, "batches": nb,
-                      "blocks_checked": checked, "erange_blocks": erange, "mismatches": 0,
+                      "blocks_checked": checked, "erange_blocks": erange, "model_blocks": modelled,
+                      "mismatches": 0,
                       "canaries": "intact"}))
 
 
