@@ -255,6 +255,44 @@ int APE_LZ4_compress_hc_withPrefix_batch_dev(const char *const *d_src, const int
                                              int depth, void *d_scratch, size_t scratch_bytes,
                                              void *stream);
 
+/* ---- high-ratio mode, cost-minimising parse (lz4_encode_hc_opt.hip) ----
+ * APE_LZ4_compress_hc_opt_batch_dev and APE_LZ4_compress_hc_opt_withPrefix_batch_dev are the two
+ * calls above with another parse over the same search: arguments, used history, depth (0..256,
+ * 0 = 64), per-block results, what is read and written, passes and errors are theirs.  THE RULE:
+ * every offset of an LZ4 block costs two bytes, so the longest match the search found at a
+ * position prices every shorter length of it too.  A backward pass over the block gives each
+ * position the bytes the rest of the block takes from there -- a literal (with the length byte
+ * it adds to the literal run it leads), or a match of any length from 4 up to the match's FULL
+ * length (the common prefix of source and position up to the block's end less 5, also past the
+ * search's cap of 272) -- and keeps the cheapest; a tie goes to the match, and among equally
+ * cheap lengths to the longest.  A forward pass emits the choices; there is no lazy step and no
+ * backward extension.  The parse is cost-minimising, not optimal: a literal is priced against
+ * the run of the chosen continuation only.  The block's size is known before its first byte is
+ * written, so a block that does not fit d_dstCap[i] writes nothing.
+ * DETERMINISM: the output bytes are a pure function of (input bytes, used history, depth) -- the
+ *   same on every call, stream, batch composition, scratch size and alignment;
+ *   tests/hcoptmodel.py defines that function on the CPU (compress(), compress_prefix()).  On
+ *   the test inputs no block is larger than the lazy parse's; the bytes differ from it.
+ * scratch : the caller's, 16-byte aligned.  scratch_size(nblocks) is what one pass over nblocks
+ *   takes -- the chain table, the match records and one cost per position, 393216 + 262144 =
+ *   655360 bytes per block, at most 1024 blocks at a time; 0 for nblocks <= 0.  A smaller
+ *   scratch, at least scratch_size(1), makes the call run several passes with identical output.
+ *   Every scratch byte the call reads it has written before, in the same call.
+ * Asynchronous, no allocation, no sync, graph-capturable: three stream-ordered launches per pass
+ * (chain build and search as above, then one kernel that prices and emits), their number
+ * decided on the host.  APE_LZ4_GPU_EINVAL before any device call as above, with this
+ * scratch_size(1). */
+size_t APE_LZ4_compress_hc_opt_scratch_size(int nblocks);
+int APE_LZ4_compress_hc_opt_batch_dev(const char *const *d_src, const int *d_srcSize,
+                                      char *const *d_dst, const int *d_dstCap, int *d_result,
+                                      int nblocks, int depth, void *d_scratch,
+                                      size_t scratch_bytes, void *stream);
+int APE_LZ4_compress_hc_opt_withPrefix_batch_dev(const char *const *d_src, const int *d_srcSize,
+                                                 const int *d_prefixSize, char *const *d_dst,
+                                                 const int *d_dstCap, int *d_result, int nblocks,
+                                                 int depth, void *d_scratch, size_t scratch_bytes,
+                                                 void *stream);
+
 /* ---- the high-ratio mode against a prepared dictionary (lz4_hc_cdict.hip) ----
  * Many independent messages, one shared dictionary, the deep search: message i is compressed
  * with the dictionary's tail as its history, without a per-message copy of the dictionary and
@@ -477,6 +515,23 @@ int APE_LZ4_compress_large_hc_timed_dev(const char *const *d_src, const int *d_s
                                         int nblocks, int maxSrcSize, int depth, void *d_scratch,
                                         size_t scratch_bytes, int restartBytes, void *stream,
                                         float *ms6);
+/* APE_LZ4_compress_large_hc_opt_batch_dev is APE_LZ4_compress_large_hc_batch_dev with the
+ * cost-minimising parse (above) on the slices: slice k gets the bytes of
+ * APE_LZ4_compress_hc_opt_withPrefix_batch_dev, an input of at most 65536 bytes those of
+ * APE_LZ4_compress_hc_opt_batch_dev.  Slicing, restart points, the seek index, the stitch, the
+ * results, the errors and the decoders that read the blocks are unchanged.
+ * DETERMINISM: a pure function of (input bytes, used history, depth, restartBytes);
+ *   tests/hcoptmodel.py compress_large() is that function.
+ * scratch : as above with 655360 bytes of tables per slice of a pass instead of 393216
+ *   (APE_LZ4_compress_large_hc_opt_scratch_size).  Plan, three launches per pass, offsets,
+ *   stitch and (with an index) one more. */
+size_t APE_LZ4_compress_large_hc_opt_scratch_size(int nblocks, int maxSrcSize, int passSlices);
+int APE_LZ4_compress_large_hc_opt_batch_dev(const char *const *d_src, const int *d_srcSize,
+                                            char *const *d_dst, const int *d_dstCap,
+                                            int *d_result, int nblocks, int maxSrcSize, int depth,
+                                            void *d_scratch, size_t scratch_bytes,
+                                            int restartBytes, void *d_index, size_t index_stride,
+                                            void *stream);
 
 /* ---- byte ranges of indexed blocks (lz4_decode.hip) ----
  * APE_LZ4_decompress_range_indexed_batch_dev decodes, for each REQUEST, the bytes

@@ -30,6 +30,8 @@ __all__ = [
     "cdict_size", "cdict_window", "cdict_prepare", "compress_cdict_batch",
     "compress_hc_scratch_size", "compress_hc_ptr_batch",
     "compress_hc_prefix_ptr_batch", "compress_large_hc_scratch_size", "compress_large_hc_ptr_batch",
+    "compress_hc_opt_scratch_size", "compress_hc_opt_ptr_batch", "compress_hc_opt_prefix_ptr_batch",
+    "compress_large_hc_opt_scratch_size", "compress_large_hc_opt_ptr_batch",
     "ONESHOT_HOST_ALL",
 ]
 
@@ -101,6 +103,11 @@ def lib():
             "APE_LZ4_compress_hc_scratch_size": (sz, [i]),
             "APE_LZ4_compress_hc_batch_dev": (i, [p, p, p, p, p, i, i, p, sz, p]),
             "APE_LZ4_compress_hc_withPrefix_batch_dev": (i, [p, p, p, p, p, p, i, i, p, sz, p]),
+            "APE_LZ4_compress_hc_opt_scratch_size": (sz, [i]),
+            "APE_LZ4_compress_hc_opt_batch_dev": (i, [p, p, p, p, p, i, i, p, sz, p]),
+            "APE_LZ4_compress_hc_opt_withPrefix_batch_dev": (i, [p, p, p, p, p, p, i, i, p, sz, p]),
+            "APE_LZ4_compress_large_hc_opt_scratch_size": (sz, [i, i, i]),
+            "APE_LZ4_compress_large_hc_opt_batch_dev": (i, [p, p, p, p, p, i, i, i, p, sz, i, p, sz, p]),
             "APE_LZ4_hc_cdict_size": (sz, []),
             "APE_LZ4_hc_cdict_window": (i, [i, i]),
             "APE_LZ4_hc_cdict_prepare_dev": (i, [p, i, i, p, sz, p]),
@@ -630,6 +637,84 @@ def compress_hc_prefix_ptr_batch(src_ptrs, src_sizes, prefix_sizes, dst_ptrs, ca
         _ptr(src_ptrs), _ptr(src_sizes), _ptr(prefix_sizes), _ptr(dst_ptrs), _ptr(caps),
         _ptr(results), n, depth, _ptr(scratch), scratch.numel(), _stream(stream)),
         "APE_LZ4_compress_hc_withPrefix_batch_dev")
+
+
+def compress_hc_opt_scratch_size(nblocks):
+    """APE_LZ4_compress_hc_opt_scratch_size: scratch bytes for one pass over nblocks."""
+    return lib().APE_LZ4_compress_hc_opt_scratch_size(nblocks)
+
+
+def compress_hc_opt_ptr_batch(src_ptrs, src_sizes, dst_ptrs, caps, results, depth, scratch,
+                              stream=None):
+    """compress_hc_ptr_batch with the cost-minimising parse over the same search (smaller or
+    equal blocks, other bytes); scratch is a uint8 CUDA tensor of at least
+    compress_hc_opt_scratch_size(1) bytes (fewer than compress_hc_opt_scratch_size(N): several
+    passes, same bytes).  Allocates nothing, so it can be graph-captured."""
+    import torch
+    what = "compress_hc_opt_ptr_batch"
+    _arr(src_sizes, what + " src_sizes", torch.int32)
+    n = src_sizes.shape[0]
+    _ptr_args(what, n, src_ptrs=(src_ptrs, _i64()), src_sizes=(src_sizes, _i32()),
+              dst_ptrs=(dst_ptrs, _i64()), caps=(caps, _i32()), results=(results, _i32()))
+    _arr(scratch, what + " scratch", torch.uint8)
+    _check(lib().APE_LZ4_compress_hc_opt_batch_dev(
+        _ptr(src_ptrs), _ptr(src_sizes), _ptr(dst_ptrs), _ptr(caps), _ptr(results), n, depth,
+        _ptr(scratch), scratch.numel(), _stream(stream)), "APE_LZ4_compress_hc_opt_batch_dev")
+
+
+def compress_hc_opt_prefix_ptr_batch(src_ptrs, src_sizes, prefix_sizes, dst_ptrs, caps, results,
+                                     depth, scratch, stream=None):
+    """compress_hc_prefix_ptr_batch with the cost-minimising parse: history, results and
+    decoding are the same; the scratch is compress_hc_opt_ptr_batch's."""
+    import torch
+    what = "compress_hc_opt_prefix_ptr_batch"
+    _arr(src_sizes, what + " src_sizes", torch.int32)
+    n = src_sizes.shape[0]
+    _ptr_args(what, n, src_ptrs=(src_ptrs, _i64()), src_sizes=(src_sizes, _i32()),
+              prefix_sizes=(prefix_sizes, (_i32(), True)), dst_ptrs=(dst_ptrs, _i64()),
+              caps=(caps, _i32()), results=(results, _i32()))
+    _arr(scratch, what + " scratch", torch.uint8)
+    _check(lib().APE_LZ4_compress_hc_opt_withPrefix_batch_dev(
+        _ptr(src_ptrs), _ptr(src_sizes), _ptr(prefix_sizes), _ptr(dst_ptrs), _ptr(caps),
+        _ptr(results), n, depth, _ptr(scratch), scratch.numel(), _stream(stream)),
+        "APE_LZ4_compress_hc_opt_withPrefix_batch_dev")
+
+
+def compress_large_hc_opt_scratch_size(nblocks, max_src_size, pass_slices=0):
+    """APE_LZ4_compress_large_hc_opt_scratch_size: the large path's scratch plus the tables of
+    the cost-minimising parse for pass_slices slices (0: as many as the batch has, at most
+    1024)."""
+    return lib().APE_LZ4_compress_large_hc_opt_scratch_size(nblocks, max_src_size, pass_slices)
+
+
+def compress_large_hc_opt_ptr_batch(src_ptrs, src_sizes, dst_ptrs, caps, results, max_src_size,
+                                    depth, restart_bytes=0, index=None, scratch=None, stream=None):
+    """compress_large_hc_ptr_batch with the cost-minimising parse on the slices: restart points,
+    the index and every decoder as there.  scratch: uint8 CUDA tensor of at least
+    compress_large_hc_opt_scratch_size(N, max_src_size, 1) bytes, 16-byte aligned; None
+    allocates one for a single pass.  Returns the scratch."""
+    import torch
+    what = "compress_large_hc_opt_ptr_batch"
+    _arr(src_sizes, what + " src_sizes", torch.int32)
+    n = src_sizes.shape[0]
+    _ptr_args(what, n, src_ptrs=(src_ptrs, _i64()), src_sizes=(src_sizes, _i32()),
+              dst_ptrs=(dst_ptrs, _i64()), caps=(caps, _i32()), results=(results, _i32()))
+    stride = 0
+    if index is not None:
+        stride = _index_arg(what, index, n)
+    if scratch is None:
+        need = compress_large_hc_opt_scratch_size(n, max_src_size)
+        if need == 0 or need >= 1 << 63:
+            raise ValueError("%s: max_src_size outside [1, 0x7E000000] or too many slices for "
+                             "one call" % what)
+        scratch = torch.empty(need, dtype=torch.uint8, device=src_sizes.device)
+    else:
+        _arr(scratch, what + " scratch", torch.uint8)
+    _check(lib().APE_LZ4_compress_large_hc_opt_batch_dev(
+        _ptr(src_ptrs), _ptr(src_sizes), _ptr(dst_ptrs), _ptr(caps), _ptr(results), n,
+        max_src_size, depth, _ptr(scratch), scratch.numel(), restart_bytes, _ptr(index), stride,
+        _stream(stream)), "APE_LZ4_compress_large_hc_opt_batch_dev")
+    return scratch
 
 
 def hc_cdict_size():

@@ -250,6 +250,18 @@ struct HcArgs {
 // chain build (one wave per block), search (one lane per position), parse + emit (one wave per
 // block)
 hipError_t launch_encode_hc(const HcArgs &a, hipStream_t s, hipEvent_t *ev = nullptr);
+// The cost-minimising parse (lz4_encode_hc_opt.hip; tests/hcoptmodel.py is the
+// definition): the chain build and the search above as they are, then a parse that prices
+// every position backward and emits forward.  It needs one more table per block, cost[p] (u32:
+// the bytes the rest of the block takes from p on), so the scratch of one block is
+// kHcOptSlotBytes.  HcArgs keeps its layout: the extra pointer travels beside it.
+constexpr size_t kHcOptSlotBytes = kHcSlotBytes + (size_t)kMaxBlock * sizeof(uint32_t);
+struct HcOptArgs {
+    HcArgs a;
+    uint32_t *cost;           // block i's at cost + i * kMaxBlock
+};
+// chain build, search, price + emit (one wave per block): three launches
+hipError_t launch_encode_hc_opt(const HcOptArgs &o, hipStream_t s, hipEvent_t *ev = nullptr);
 
 // ---- prepared high-ratio dictionary (lz4_hc_cdict.hip) ----
 // The window of message m is [the dictionary's last D bytes | m], D = min(dictSize, 65536 -
@@ -382,9 +394,11 @@ hipError_t launch_large(const LargeArgs &a, int accel, hipStream_t s, hipEvent_t
 // over the slot arrays in passes of `pass` slots (1..1024) on the chain and match tables at
 // `hc` (pass * kHcSlotBytes bytes).  ev (nullable): 5 + 3 * passes events, recorded before the
 // plan, after it, after each pass's chain, search and parse, and after offsets, stitch, index.
+// opt: the cost-minimising parse on the slices; `hc` then holds the cost tables
+// after the chain and match tables (pass * kHcOptSlotBytes bytes).
 inline int large_hc_passes(int nslots, int pass) { return (nslots + pass - 1) / pass; }
 hipError_t launch_large_hc(const LargeArgs &a, int depth, void *hc, int pass, hipStream_t s,
-                           hipEvent_t *ev = nullptr);
+                           hipEvent_t *ev = nullptr, bool opt = false);
 hipError_t launch_synth(char *out, size_t stride, int n, long long first, int nblocks,
                         int kind, hipStream_t s);
 

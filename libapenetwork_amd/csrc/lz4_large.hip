@@ -381,8 +381,10 @@ hipError_t launch_large(const LargeArgs &a, int accel, hipStream_t s, hipEvent_t
 // final run, whichever encoder wrote them.  The plan's s_prefix is the history OFFERED (back to
 // the input's start or the last restart point); the high-ratio kernels use min(that, 65536 -
 // size) of it.  An absent slot has size -1: its parse wave writes result 0 and reads nothing.
+// opt picks the slices' parse: the lazy one, or the cost-minimising one, whose
+// cost tables follow the match tables at `hc`.
 hipError_t launch_large_hc(const LargeArgs &a, int depth, void *hc, int pass, hipStream_t s,
-                           hipEvent_t *ev) {
+                           hipEvent_t *ev, bool opt) {
     if (a.nblocks <= 0) return hipSuccess;
     int q = 0;
     auto mark = [&]() { return ev ? hipEventRecord(ev[q++], s) : hipSuccess; };
@@ -404,7 +406,14 @@ hipError_t launch_large_hc(const LargeArgs &a, int depth, void *hc, int pass, hi
         h.depth = depth;
         h.chain = (uint16_t *)hc;
         h.match = (uint32_t *)((char *)hc + (size_t)pass * kHcChainBytes);
-        e = launch_encode_hc(h, s, ev ? ev + q : nullptr);
+        if (opt) {
+            HcOptArgs o{};
+            o.a = h;
+            o.cost = (uint32_t *)((char *)hc + (size_t)pass * kHcSlotBytes);
+            e = launch_encode_hc_opt(o, s, ev ? ev + q : nullptr);
+        } else {
+            e = launch_encode_hc(h, s, ev ? ev + q : nullptr);
+        }
         if (ev) q += 3;
     }
     if (e != hipSuccess) return e;

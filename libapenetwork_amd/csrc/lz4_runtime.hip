@@ -524,23 +524,30 @@ size_t APE_LZ4_compress_hc_scratch_size(int nblocks) {
     return (size_t)(nblocks < kHcSub ? nblocks : kHcSub) * kHcSlotBytes;
 }
 
+size_t APE_LZ4_compress_hc_opt_scratch_size(int nblocks) {
+    if (nblocks <= 0) return 0;
+    return (size_t)(nblocks < kHcSub ? nblocks : kHcSub) * kHcOptSlotBytes;
+}
+
 namespace {
-// d_prefixSize (nullable): per-block bytes of history before d_src[i]
-int hc_batch(const char *what, const char *const *d_src, const int *d_srcSize,
+// d_prefixSize (nullable): per-block bytes of history before d_src[i]; opt: the cost-minimising
+// parse (lz4_encode_hc_opt.hip), whose cost tables follow the match tables in the scratch
+int hc_batch(const char *what, bool opt, const char *const *d_src, const int *d_srcSize,
              const int *d_prefixSize, char *const *d_dst, const int *d_dstCap, int *d_result,
              int nblocks, int depth, void *d_scratch, size_t scratch_bytes, void *stream) {
+    const size_t slot = opt ? kHcOptSlotBytes : kHcSlotBytes;
     if (nblocks < 0 || depth < 0 || depth > kHcMaxDepth || !d_scratch ||
-        ((uintptr_t)d_scratch & 15u) || scratch_bytes < kHcSlotBytes ||
+        ((uintptr_t)d_scratch & 15u) || scratch_bytes < slot ||
         (nblocks > 0 && (!d_src || !d_srcSize || !d_dst || !d_dstCap || !d_result))) {
         snprintf(g_err, sizeof g_err, "%s: nblocks %d, depth %d (0..%d), scratch of %zu "
                  "bytes at %p (need %zu bytes, 16-byte aligned)", what, nblocks, depth,
-                 kHcMaxDepth, scratch_bytes, d_scratch, kHcSlotBytes);
+                 kHcMaxDepth, scratch_bytes, d_scratch, slot);
         return APE_LZ4_GPU_EINVAL;
     }
     int rc = check_device();
     if (rc) return rc;
     // as many blocks per pass as the caller's scratch holds
-    const size_t fit = scratch_bytes / kHcSlotBytes;
+    const size_t fit = scratch_bytes / slot;
     int sub = fit < (size_t)kHcSub ? (int)fit : kHcSub;
     if (sub > nblocks) sub = nblocks;
     hipError_t e = hipSuccess;
@@ -556,18 +563,45 @@ int hc_batch(const char *what, const char *const *d_src, const int *d_srcSize,
         a.depth = depth ? depth : kHcDefaultDepth;
         a.chain = (uint16_t *)d_scratch;
         a.match = (uint32_t *)((char *)d_scratch + (size_t)sub * kHcChainBytes);
-        e = launch_encode_hc(a, (hipStream_t)stream);
+        if (opt) {
+            HcOptArgs o{};
+            o.a = a;
+            o.cost = (uint32_t *)((char *)d_scratch + (size_t)sub * kHcSlotBytes);
+            e = launch_encode_hc_opt(o, (hipStream_t)stream);
+        } else {
+            e = launch_encode_hc(a, (hipStream_t)stream);
+        }
     }
-    return finish_launch(e, "lz4_hc_chain_kernel + lz4_hc_search_kernel + lz4_hc_parse_kernel");
+    return finish_launch(e, opt ? "lz4_hc_chain_kernel + lz4_hc_search_kernel + "
+                                  "lz4_hc_opt_parse_kernel"
+                                : "lz4_hc_chain_kernel + lz4_hc_search_kernel + "
+                                  "lz4_hc_parse_kernel");
 }
 }  // namespace
+
+int APE_LZ4_compress_hc_opt_batch_dev(const char *const *d_src, const int *d_srcSize,
+                                      char *const *d_dst, const int *d_dstCap, int *d_result,
+                                      int nblocks, int depth, void *d_scratch,
+                                      size_t scratch_bytes, void *stream) {
+    return hc_batch("compress_hc_opt", true, d_src, d_srcSize, nullptr, d_dst, d_dstCap, d_result,
+                    nblocks, depth, d_scratch, scratch_bytes, stream);
+}
+
+int APE_LZ4_compress_hc_opt_withPrefix_batch_dev(const char *const *d_src, const int *d_srcSize,
+                                                 const int *d_prefixSize, char *const *d_dst,
+                                                 const int *d_dstCap, int *d_result, int nblocks,
+                                                 int depth, void *d_scratch, size_t scratch_bytes,
+                                                 void *stream) {
+    return hc_batch("compress_hc_opt_withPrefix", true, d_src, d_srcSize, d_prefixSize, d_dst,
+                    d_dstCap, d_result, nblocks, depth, d_scratch, scratch_bytes, stream);
+}
 
 int APE_LZ4_compress_hc_batch_dev(const char *const *d_src, const int *d_srcSize,
                                   char *const *d_dst, const int *d_dstCap, int *d_result,
                                   int nblocks, int depth, void *d_scratch, size_t scratch_bytes,
                                   void *stream) {
-    return hc_batch("compress_hc", d_src, d_srcSize, nullptr, d_dst, d_dstCap, d_result, nblocks,
-                    depth, d_scratch, scratch_bytes, stream);
+    return hc_batch("compress_hc", false, d_src, d_srcSize, nullptr, d_dst, d_dstCap, d_result,
+                    nblocks, depth, d_scratch, scratch_bytes, stream);
 }
 
 int APE_LZ4_compress_hc_withPrefix_batch_dev(const char *const *d_src, const int *d_srcSize,
@@ -575,8 +609,8 @@ int APE_LZ4_compress_hc_withPrefix_batch_dev(const char *const *d_src, const int
                                              const int *d_dstCap, int *d_result, int nblocks,
                                              int depth, void *d_scratch, size_t scratch_bytes,
                                              void *stream) {
-    return hc_batch("compress_hc_withPrefix", d_src, d_srcSize, d_prefixSize, d_dst, d_dstCap,
-                    d_result, nblocks, depth, d_scratch, scratch_bytes, stream);
+    return hc_batch("compress_hc_withPrefix", false, d_src, d_srcSize, d_prefixSize, d_dst,
+                    d_dstCap, d_result, nblocks, depth, d_scratch, scratch_bytes, stream);
 }
 
 // ---- the high-ratio mode against a prepared dictionary (lz4_hc_cdict.hip) ----
@@ -897,36 +931,39 @@ int large_hc_pass(long long nslots, long long want) {
     return (int)want;
 }
 
-int large_hc_batch(const char *const *d_src, const int *d_srcSize, char *const *d_dst,
+int large_hc_batch(bool opt, const char *const *d_src, const int *d_srcSize, char *const *d_dst,
                    const int *d_dstCap, int *d_result, int nblocks, int maxSrcSize, int depth,
                    void *d_scratch, size_t scratch_bytes, int restartBytes, void *d_index,
                    size_t index_stride, void *stream, float *ms6) {
+    const char *name = opt ? "compress_large_hc_opt" : "compress_large_hc";
+    const size_t slot = opt ? kHcOptSlotBytes : kHcSlotBytes;
     if (nblocks < 0 || (nblocks > 0 && (!d_src || !d_srcSize || !d_dst || !d_dstCap ||
                                          !d_result || !d_scratch))) {
-        snprintf(g_err, sizeof g_err, "compress_large_hc: invalid argument (a null array or a "
-                 "negative count)");
+        snprintf(g_err, sizeof g_err, "%s: invalid argument (a null array or a "
+                 "negative count)", name);
         return APE_LZ4_GPU_EINVAL;
     }
     if (depth < 0 || depth > kHcMaxDepth) {
-        snprintf(g_err, sizeof g_err, "compress_large_hc: depth %d outside 0..%d", depth,
+        snprintf(g_err, sizeof g_err, "%s: depth %d outside 0..%d", name, depth,
                  kHcMaxDepth);
         return APE_LZ4_GPU_EINVAL;
     }
     if (maxSrcSize < 1 || maxSrcSize > kLargeMaxSrc) {
-        snprintf(g_err, sizeof g_err, "compress_large_hc: maxSrcSize %d outside [1, %d]",
+        snprintf(g_err, sizeof g_err, "%s: maxSrcSize %d outside [1, %d]", name,
                  maxSrcSize, kLargeMaxSrc);
         return APE_LZ4_GPU_EINVAL;
     }
     if (!restart_ok(restartBytes)) {
-        snprintf(g_err, sizeof g_err, "compress_large_hc: restartBytes %d is neither 0 nor a "
-                 "positive multiple of the slice size %d", restartBytes, large_slice_size());
+        snprintf(g_err, sizeof g_err, "%s: restartBytes %d is neither 0 nor a "
+                 "positive multiple of the slice size %d", name, restartBytes,
+                 large_slice_size());
         return APE_LZ4_GPU_EINVAL;
     }
     if (d_index && (((uintptr_t)d_index & 15u) || index_stride % 16u ||
                     index_stride < large_index_size(maxSrcSize, restartBytes))) {
-        snprintf(g_err, sizeof g_err, "compress_large_hc: index at %p with stride %zu, need "
-                 "16-byte alignment and a stride that is a multiple of 16 and >= %zu", d_index,
-                 index_stride, large_index_size(maxSrcSize, restartBytes));
+        snprintf(g_err, sizeof g_err, "%s: index at %p with stride %zu, need "
+                 "16-byte alignment and a stride that is a multiple of 16 and >= %zu", name,
+                 d_index, index_stride, large_index_size(maxSrcSize, restartBytes));
         return APE_LZ4_GPU_EINVAL;
     }
     size_t base = 0;
@@ -945,13 +982,14 @@ int large_hc_batch(const char *const *d_src, const int *d_srcSize, char *const *
         a.buf = (char *)d_scratch;
         base = up16z(large_scratch_layout(nblocks, maxSrcSize, &a));
         if (base == 0) {
-            snprintf(g_err, sizeof g_err, "compress_large_hc: %d inputs of up to %d bytes are "
-                     "more slices than one call takes; split the batch", nblocks, maxSrcSize);
+            snprintf(g_err, sizeof g_err, "%s: %d inputs of up to %d bytes are "
+                     "more slices than one call takes; split the batch", name, nblocks,
+                     maxSrcSize);
             return APE_LZ4_GPU_EINVAL;
         }
-        if (scratch_bytes < base + kHcSlotBytes || ((uintptr_t)d_scratch & 15u)) {
-            snprintf(g_err, sizeof g_err, "compress_large_hc: scratch of %zu bytes at %p, need "
-                     "%zu bytes 16-byte aligned", scratch_bytes, d_scratch, base + kHcSlotBytes);
+        if (scratch_bytes < base + slot || ((uintptr_t)d_scratch & 15u)) {
+            snprintf(g_err, sizeof g_err, "%s: scratch of %zu bytes at %p, need "
+                     "%zu bytes 16-byte aligned", name, scratch_bytes, d_scratch, base + slot);
             return APE_LZ4_GPU_EINVAL;
         }
     }
@@ -959,11 +997,13 @@ int large_hc_batch(const char *const *d_src, const int *d_srcSize, char *const *
     if (rc) return rc;
     if (nblocks == 0) return APE_LZ4_GPU_OK;
     // as many slices per pass as the caller's scratch holds
-    const int pass = large_hc_pass(a.nslots, (long long)((scratch_bytes - base) / kHcSlotBytes));
+    const int pass = large_hc_pass(a.nslots, (long long)((scratch_bytes - base) / slot));
     const char *what = "large plan + lz4_hc kernels + offsets + stitch";
     const hipStream_t s = (hipStream_t)stream;
     const int d = depth ? depth : kHcDefaultDepth;
-    if (!ms6) return finish_launch(launch_large_hc(a, d, (char *)d_scratch + base, pass, s), what);
+    if (!ms6)
+        return finish_launch(launch_large_hc(a, d, (char *)d_scratch + base, pass, s, nullptr, opt),
+                             what);
     // the timed form: events around every launch, the passes' times summed per kernel
     const int passes = large_hc_passes(a.nslots, pass), nev = 5 + 3 * passes;
     std::vector<hipEvent_t> ev((size_t)nev, nullptr);
@@ -971,7 +1011,8 @@ int large_hc_batch(const char *const *d_src, const int *d_srcSize, char *const *
     for (int q = 0; q < nev && e == hipSuccess; q++) e = hipEventCreate(&ev[q]);
     rc = e == hipSuccess ? APE_LZ4_GPU_OK : finish_launch(e, "hipEventCreate");
     if (rc == APE_LZ4_GPU_OK)
-        rc = finish_launch(launch_large_hc(a, d, (char *)d_scratch + base, pass, s, ev.data()), what);
+        rc = finish_launch(launch_large_hc(a, d, (char *)d_scratch + base, pass, s, ev.data(), opt),
+                           what);
     for (int q = 0; q < 6; q++) ms6[q] = 0.f;
     if (rc == APE_LZ4_GPU_OK) {
         e = hipEventSynchronize(ev[nev - 1]);
@@ -993,13 +1034,34 @@ int large_hc_batch(const char *const *d_src, const int *d_srcSize, char *const *
 }
 }  // namespace
 
-size_t APE_LZ4_compress_large_hc_scratch_size(int nblocks, int maxSrcSize, int passSlices) {
+namespace {
+size_t large_hc_scratch(int nblocks, int maxSrcSize, int passSlices, size_t slot) {
     if (nblocks < 0 || maxSrcSize < 1 || maxSrcSize > kLargeMaxSrc || passSlices < 0) return 0;
     const size_t base = large_scratch_layout(nblocks, maxSrcSize, nullptr);
     if (!base) return (size_t)-1;   // more slice slots than one call takes: split the batch
     const long long S = large_slice_size();
     const long long nsl = maxSrcSize <= kMaxBlock ? 1 : ((long long)maxSrcSize + S - 1) / S;
-    return up16z(base) + (size_t)large_hc_pass(nblocks * nsl, passSlices) * kHcSlotBytes;
+    return up16z(base) + (size_t)large_hc_pass(nblocks * nsl, passSlices) * slot;
+}
+}  // namespace
+
+size_t APE_LZ4_compress_large_hc_scratch_size(int nblocks, int maxSrcSize, int passSlices) {
+    return large_hc_scratch(nblocks, maxSrcSize, passSlices, kHcSlotBytes);
+}
+
+size_t APE_LZ4_compress_large_hc_opt_scratch_size(int nblocks, int maxSrcSize, int passSlices) {
+    return large_hc_scratch(nblocks, maxSrcSize, passSlices, kHcOptSlotBytes);
+}
+
+int APE_LZ4_compress_large_hc_opt_batch_dev(const char *const *d_src, const int *d_srcSize,
+                                            char *const *d_dst, const int *d_dstCap,
+                                            int *d_result, int nblocks, int maxSrcSize, int depth,
+                                            void *d_scratch, size_t scratch_bytes,
+                                            int restartBytes, void *d_index, size_t index_stride,
+                                            void *stream) {
+    return large_hc_batch(true, d_src, d_srcSize, d_dst, d_dstCap, d_result, nblocks, maxSrcSize,
+                          depth, d_scratch, scratch_bytes, restartBytes, d_index, index_stride,
+                          stream, nullptr);
 }
 
 int APE_LZ4_compress_large_hc_batch_dev(const char *const *d_src, const int *d_srcSize,
@@ -1007,9 +1069,9 @@ int APE_LZ4_compress_large_hc_batch_dev(const char *const *d_src, const int *d_s
                                         int nblocks, int maxSrcSize, int depth, void *d_scratch,
                                         size_t scratch_bytes, int restartBytes, void *d_index,
                                         size_t index_stride, void *stream) {
-    return large_hc_batch(d_src, d_srcSize, d_dst, d_dstCap, d_result, nblocks, maxSrcSize, depth,
-                          d_scratch, scratch_bytes, restartBytes, d_index, index_stride, stream,
-                          nullptr);
+    return large_hc_batch(false, d_src, d_srcSize, d_dst, d_dstCap, d_result, nblocks, maxSrcSize,
+                          depth, d_scratch, scratch_bytes, restartBytes, d_index, index_stride,
+                          stream, nullptr);
 }
 
 int APE_LZ4_compress_large_hc_timed_dev(const char *const *d_src, const int *d_srcSize,
@@ -1018,8 +1080,8 @@ int APE_LZ4_compress_large_hc_timed_dev(const char *const *d_src, const int *d_s
                                         size_t scratch_bytes, int restartBytes, void *stream,
                                         float *ms6) {
     if (!ms6) return APE_LZ4_GPU_EINVAL;
-    return large_hc_batch(d_src, d_srcSize, d_dst, d_dstCap, d_result, nblocks, maxSrcSize, depth,
-                          d_scratch, scratch_bytes, restartBytes, nullptr, 0, stream, ms6);
+    return large_hc_batch(false, d_src, d_srcSize, d_dst, d_dstCap, d_result, nblocks, maxSrcSize,
+                          depth, d_scratch, scratch_bytes, restartBytes, nullptr, 0, stream, ms6);
 }
 
 int APE_LZ4_compress_batch_strided_dev(const char *d_src, size_t src_stride, const int *d_srcSize,
