@@ -348,6 +348,32 @@ int APE_LZ4_compress_hc_usingCDict_batch_dev(const char *const *d_src, const int
                                              int maxSrcSize, int depth, void *d_scratch,
                                              size_t scratch_bytes, void *stream);
 
+/* ---- the cost-minimising parse against a prepared high-ratio dictionary (lz4_hc_cdict.hip) ----
+ * APE_LZ4_compress_hc_usingCDict_batch_dev with the parse of APE_LZ4_compress_hc_opt_batch_dev:
+ * the same object (APE_LZ4_hc_cdict_prepare_dev; there is no other kind and no other prepare),
+ * the same chains and search, then every message position priced backward and the choices
+ * emitted forward.  THE BYTES are exactly those APE_LZ4_compress_hc_opt_withPrefix_batch_dev
+ * writes for the staged window [dictionary's last D bytes | message] with prefix D: a pure
+ * function of (message, those D bytes, depth), tests/hcoptdictmodel.py on the CPU.  Each block
+ * decodes with decompress_safe_usingDict given the CALLER'S ORIGINAL dictionary; with D = 0 the
+ * bytes are APE_LZ4_compress_hc_opt_batch_dev's; a message shorter than 13 bytes is one literal
+ * run.  Arguments, the header check, per-block results and APE_LZ4_GPU_EINVAL are
+ * compress_hc_usingCDict's, with one difference: the block's size is known before its first
+ * byte is written, so a block that does not fit d_dstCap[i] gets result 0 and NOTHING is written
+ * to d_dst[i].
+ * scratch : compress_hc_usingCDict's slot plus a u32 cost per message position, rounded to 16
+ *   bytes -- about 10 x maxSrcSize bytes per message -- for the same number of messages per
+ *   pass; 0 for nblocks <= 0 or maxSrcSize out of range.  A scratch of at least scratch_size(1,
+ *   maxSrcSize) runs as many passes as it needs with identical bytes.  Every scratch byte the
+ *   call reads it has written before, in the same call.  No allocation, no sync: three
+ *   stream-ordered launches per pass, graph-capturable. */
+size_t APE_LZ4_compress_hc_opt_usingCDict_scratch_size(int nblocks, int maxSrcSize);
+int APE_LZ4_compress_hc_opt_usingCDict_batch_dev(const char *const *d_src, const int *d_srcSize,
+                                                 char *const *d_dst, const int *d_dstCap,
+                                                 int *d_result, int nblocks, const void *d_cdict,
+                                                 int maxSrcSize, int depth, void *d_scratch,
+                                                 size_t scratch_bytes, void *stream);
+
 /* ---- inputs larger than one encoder block, as ONE LZ4 block (lz4_large.hip) ----
  * == N x APE_LZ4_compress_fast on inputs of any size up to maxSrcSize: d_result[i] <-
  * size of ONE valid LZ4 block of d_src[i][0, d_srcSize[i]) (decodes with decompress_safe,

@@ -32,6 +32,7 @@ __all__ = [
     "compress_hc_prefix_ptr_batch", "compress_large_hc_scratch_size", "compress_large_hc_ptr_batch",
     "compress_hc_opt_scratch_size", "compress_hc_opt_ptr_batch", "compress_hc_opt_prefix_ptr_batch",
     "compress_large_hc_opt_scratch_size", "compress_large_hc_opt_ptr_batch",
+    "compress_hc_opt_cdict_scratch_size", "compress_hc_opt_cdict_batch",
     "ONESHOT_HOST_ALL",
 ]
 
@@ -113,6 +114,8 @@ def lib():
             "APE_LZ4_hc_cdict_prepare_dev": (i, [p, i, i, p, sz, p]),
             "APE_LZ4_compress_hc_usingCDict_scratch_size": (sz, [i, i]),
             "APE_LZ4_compress_hc_usingCDict_batch_dev": (i, [p, p, p, p, p, i, p, i, i, p, sz, p]),
+            "APE_LZ4_compress_hc_opt_usingCDict_scratch_size": (sz, [i, i]),
+            "APE_LZ4_compress_hc_opt_usingCDict_batch_dev": (i, [p, p, p, p, p, i, p, i, i, p, sz, p]),
             "APE_LZ4_compress_large_hc_scratch_size": (sz, [i, i, i]),
             "APE_LZ4_compress_large_hc_batch_dev": (i, [p, p, p, p, p, i, i, i, p, sz, i, p, sz, p]),
             "APE_LZ4_compress_large_hc_timed_dev": (i, [p, p, p, p, p, i, i, i, p, sz, i, p, p]),
@@ -768,6 +771,34 @@ def compress_hc_cdict_batch(src_ptrs, src_sizes, dst_ptrs, caps, results, cdict,
         _ptr(src_ptrs), _ptr(src_sizes), _ptr(dst_ptrs), _ptr(caps), _ptr(results), n,
         _ptr(cdict), max_src_size, depth, _ptr(scratch), scratch.numel(), _stream(stream)),
         "APE_LZ4_compress_hc_usingCDict_batch_dev")
+
+
+def compress_hc_opt_cdict_scratch_size(nblocks, max_src_size):
+    """APE_LZ4_compress_hc_opt_usingCDict_scratch_size: scratch bytes for one pass over nblocks."""
+    return lib().APE_LZ4_compress_hc_opt_usingCDict_scratch_size(nblocks, max_src_size)
+
+
+def compress_hc_opt_cdict_batch(src_ptrs, src_sizes, dst_ptrs, caps, results, cdict, max_src_size,
+                                depth, scratch, stream=None):
+    """compress_hc_cdict_batch with the cost-minimising parse of compress_hc_opt_ptr_batch: the
+    same object, arguments and decoding.  scratch is a uint8 CUDA tensor of at least
+    compress_hc_opt_cdict_scratch_size(1, max_src_size) bytes (fewer than ..._scratch_size(N,
+    ...): several passes, same bytes).  A block that does not fit its capacity gets result 0
+    and nothing is written to it.  Allocates nothing, so it can be graph-captured."""
+    import torch
+    what = "compress_hc_opt_cdict_batch"
+    _arr(src_sizes, what + " src_sizes", torch.int32)
+    n = src_sizes.shape[0]
+    _ptr_args(what, n, src_ptrs=(src_ptrs, _i64()), src_sizes=(src_sizes, _i32()),
+              dst_ptrs=(dst_ptrs, _i64()), caps=(caps, _i32()), results=(results, _i32()))
+    _arr(cdict, what + " cdict", torch.uint8)
+    if cdict.numel() < hc_cdict_size():
+        raise ValueError(what + " cdict: smaller than hc_cdict_size()")
+    _arr(scratch, what + " scratch", torch.uint8)
+    _check(lib().APE_LZ4_compress_hc_opt_usingCDict_batch_dev(
+        _ptr(src_ptrs), _ptr(src_sizes), _ptr(dst_ptrs), _ptr(caps), _ptr(results), n,
+        _ptr(cdict), max_src_size, depth, _ptr(scratch), scratch.numel(), _stream(stream)),
+        "APE_LZ4_compress_hc_opt_usingCDict_batch_dev")
 
 
 def compress_large_hc_scratch_size(nblocks, max_src_size, pass_slices=0):

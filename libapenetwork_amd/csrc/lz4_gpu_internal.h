@@ -314,6 +314,21 @@ hipError_t launch_hc_cdict_prepare(const char *dict, int dict_size, int max_src,
 // chain build (one wave per message), search (one lane per message position), parse + emit
 // (one wave per message)
 hipError_t launch_encode_hc_cdict(const HcDictArgs &a, hipStream_t s);
+// The cost-minimising parse against the same object (tests/hcoptdictmodel.py is
+// the definition): the chain build and the search above as they are, then a parse that prices
+// every message position backward and emits forward.  One more table per message, cost[p] (u32:
+// the bytes the rest of the message takes from position p on).  HcDictArgs keeps its layout.
+inline size_t hc_cdict_cost_entries(int max_src) { return ((size_t)max_src + 3) & ~(size_t)3; }
+inline size_t hc_cdict_opt_slot_bytes(int max_src) {
+    return hc_cdict_slot_bytes(max_src) + hc_cdict_cost_entries(max_src) * sizeof(uint32_t);
+}
+struct HcDictOptArgs {
+    HcDictArgs a;
+    uint32_t *cost;           // message i's at cost + i * cost_stride (entries)
+    uint32_t cost_stride;
+};
+// chain build, search, price + emit (one wave per message): three launches
+hipError_t launch_encode_hc_cdict_opt(const HcDictOptArgs &o, hipStream_t s);
 // compress_destSize pass 2 (lz4_destsize.hip): scratch slot i (at scratch + i*stride, encoder
 // result sres[i]) -> dst[i] cut to target[i]; src_size[i] <- consumed input
 hipError_t launch_destsize(const char *const *src, int *src_size, char *const *dst,

@@ -9,6 +9,8 @@
 // (the first three straddle dictionary and message).  A chain walk follows the object's
 // chain[] below D - 3 and the message's scratch from there on.  The search and the parse are
 // lz4_encode_hc.hip's, rule for rule, with loads that pick their side of the boundary.
+// APE_LZ4_compress_hc_opt_usingCDict_batch_dev runs the same chain build and
+// search and then lz4_encode_hc_opt.hip's cost-minimising parse, in message positions.
 //
 // Every kernel checks the object's header before it uses anything else of it.  Every load of a
 // message stays inside src[0, n), every load of the object inside it, every store inside
@@ -351,6 +353,245 @@ __global__ void __launch_bounds__(64) lz4_hc_cdict_parse_kernel(HcDictArgs a) {
     if (lane == 0) a.result[b] = result;
 }
 
+// ---- price + emit (the cost-minimising parse) ----
+// lz4_hc_opt_parse_kernel's rule in message positions (lz4_encode_hc_opt.hip describes the
+// registers and the run shortcut; tests/hcoptdictmodel.py is the definition): cost[] and match[]
+// are indexed by message position, a match's source is a window position, and only the
+// extension of a capped match reads its source, on whichever side of the boundary it lies.
+
+// what this wave's lanes stored to global memory so far is what any of its lanes loads from here
+// on (lz4_encode_hc_opt.hip's)
+__device__ __forceinline__ void own_stores_visible() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+}
+
+// len_bytes() for this kernel alone.  The compiler derives value ranges for a shared helper from
+// all of its call sites, so calling len_bytes() here would change the instructions it emits for
+// lz4_hc_cdict_parse_kernel, which stays exactly as it was (profiles/hc_opt_cdict_asm_diff.txt).
+__device__ __forceinline__ uint32_t opt_len_bytes(uint32_t v) {
+    return v >= 15u ? (v - 15u) / 255u + 1u : 0u;
+}
+
+// the common prefix of the message from sp on and the window from q on, from L on and at most
+// lim (sp + lim <= n - 5): 8 bytes per lane while the source's 8 lie on one side, byte by byte
+// across the boundary and at the end
+__device__ __forceinline__ uint32_t extend(const Window &W, uint32_t sp, uint32_t q, uint32_t L,
+                                           uint32_t lim, int lane) {
+    while (L < lim) {
+        const uint32_t o = L + 8u * (uint32_t)lane;
+        const int qo = (int)(q + o);
+        uint32_t cnt = 0u;
+        if (o + 8u <= lim && W.one_side(qo, 8)) {
+            const uint2 u = gload8(W.msg + sp + o), v = gload8(W.at(qo));
+            const uint32_t d0 = u.x ^ v.x, d1 = u.y ^ v.y;
+            cnt = d0 ? first_diff(d0) : d1 ? 4u + first_diff(d1) : 8u;
+        } else {
+            while (cnt < 8u && o + cnt < lim && W.msg[sp + o + cnt] == W.byte(qo + (int)cnt)) cnt++;
+        }
+        const uint64_t part = wave_ballot(cnt < 8u);
+        if (!part) {
+            L += 512u;
+            continue;
+        }
+        const int fl = __builtin_ctzll(part);
+        L += 8u * (uint32_t)fl + lane_val(cnt, fl);
+        break;
+    }
+    return umin(L, lim);
+}
+
+__global__ void __launch_bounds__(64) lz4_hc_cdict_opt_parse_kernel(HcDictOptArgs o) {
+    const HcDictArgs &a = o.a;
+    const int b = blockIdx.x, lane = lane_id();
+    const int n = a.src_size[b], cap = a.dst_cap[b];
+    Window W;
+    const bool ok = open_object(a, &W, b);
+    if (!ok || n < 0 || n > a.max_src || cap <= 0) {
+        if (lane == 0) a.result[b] = ok && n > a.max_src ? kErange : 0;
+        return;
+    }
+    gcu8 *src = W.msg;
+    gu8 *dst = (gu8 *)a.dst[b];
+    uint32_t *M = a.match + (size_t)b * a.match_stride;
+    uint32_t *A = o.cost + (size_t)b * o.cost_stride;
+    const uint32_t un = (uint32_t)n, ucap = (uint32_t)cap, uD = (uint32_t)W.D;
+    const uint32_t last = un - (uint32_t)kMFLimit, end = un - (uint32_t)kLastLiterals;
+
+    // ---- backward: the cost of every message position, and its choice ----
+    uint32_t total = 1u + un + opt_len_bytes(un);   // one literal run
+    if (n >= kMinLength) {
+        uint32_t a1 = 1u, r1 = 0u;   // cost[p + 1] (cost[n] = 1: the final run's token), and the
+                                     // literals that lead it
+        // the capped match last extended past the cap: its offset, position, end and cost[end]
+        uint32_t run_off = 0u, run_p = 0u, run_end = 0u, run_a = 0u;
+        // near0 lane i holds cost[hi - i] (as far as priced), near<c> lane i cost[hi + 64 c - i]
+        uint32_t near1 = 0u, near2 = 0u, near3 = 0u, near4 = 0u, near5 = 0u;
+        for (int hi = n - 1; hi >= 0; hi -= 64) {
+            const int pos = hi - lane;
+            const bool valid = pos >= 0;
+            const uint32_t m = valid && (uint32_t)pos <= last ? M[pos] : 0u;
+            const int cnt = min(64, hi + 1);
+            uint32_t near0 = 0u, my_c = 0u;
+            for (int j = 0; j < cnt; j++) {
+                const uint32_t p = (uint32_t)(hi - j);
+                const uint32_t mm = lane_val(m, j);
+                const uint32_t L = mm >> 16, q = mm & 0xFFFFu;   // q: a window position
+                const uint32_t r2 = r1 + 1u;
+                // a literal: its byte, and the length byte it adds to the run it leads
+                const uint32_t lit = 1u + a1 + (r2 >= 15u && (r2 - 15u) % 255u == 0u ? 1u : 0u);
+                uint32_t choice = 0u, cost = lit;
+                if (L >= (uint32_t)kMinMatch) {
+                    const uint32_t lim = end - p;
+                    uint32_t E = L, far = 0u;
+                    if (L == (uint32_t)kHcCap && lim > (uint32_t)kHcCap) {
+                        // capped by the search: the full length, from the run this match
+                        // continues (whichever side its source lies on) or by extension
+                        const uint32_t off = uD + p - q;
+                        if (off == run_off && run_p <= p + L) {
+                            E = run_end - p;
+                            far = run_a;
+                            run_p = p;
+                        } else {
+                            E = extend(W, p, q, L, lim, lane);
+                            run_off = 0u;   // (an extension that ends at the cap starts no run)
+                            if (E > (uint32_t)kHcCap) {
+                                own_stores_visible();
+                                far = __hip_atomic_load(A + p + E, __ATOMIC_RELAXED,
+                                                        __HIP_MEMORY_SCOPE_AGENT);
+                                run_off = off;
+                                run_p = p;
+                                run_end = p + E;
+                                run_a = far;
+                            }
+                        }
+                    }
+                    // lengths 4 .. L: the least cost, then the longest (the key and its
+                    // reduction are lz4_hc_opt_parse_kernel's)
+                    const uint32_t uj = (uint32_t)j;
+                    auto cand = [&](uint32_t c, uint32_t base) {
+                        const uint32_t l = base - (uint32_t)lane;   // (wraps for an unpriced lane)
+                        const uint32_t inv = 0xFFFFF800u - ((c + (l >= 19u ? 1u : 0u)) << 9) + l;
+                        return l - (uint32_t)kMinMatch <= L - (uint32_t)kMinMatch ? inv : 0u;
+                    };
+                    uint32_t best = cand(near0, uj);
+                    if (uj + 1u <= L) {
+                        best = umax(best, cand(near1, uj + 64u));
+                        if (uj + 65u <= L) {
+                            best = umax(best, cand(near2, uj + 128u));
+                            if (uj + 129u <= L) {
+                                best = umax(best, cand(near3, uj + 192u));
+                                if (uj + 193u <= L) {
+                                    best = umax(best, cand(near4, uj + 256u));
+                                    if (uj + 257u <= L) best = umax(best, cand(near5, uj + 320u));
+                                }
+                            }
+                        }
+                    }
+                    const uint32_t key = ~lane_val(wave_incl_max(best), 63);
+                    uint32_t mc = key >> 9, ml = 511u - (key & 511u);
+                    if (E > (uint32_t)kHcCap) {   // the one far candidate
+                        const uint32_t fc = 3u + opt_len_bytes(E - (uint32_t)kMinMatch) + far;
+                        if (fc <= mc) {
+                            mc = fc;
+                            ml = E;
+                        }
+                    }
+                    if (mc <= lit) {   // a tie goes to the match
+                        choice = ml;
+                        cost = mc;
+                    }
+                }
+                a1 = cost;
+                r1 = choice ? 0u : r2;
+                if (lane == j) {
+                    near0 = cost;
+                    my_c = choice ? choice << 16 | q : 0u;
+                }
+            }
+            if (valid) {
+                A[pos] = near0;
+                if ((uint32_t)pos <= last) M[pos] = my_c;
+            }
+            near5 = near4;
+            near4 = near3;
+            near3 = near2;
+            near2 = near1;
+            near1 = near0;
+        }
+        total = a1;
+        own_stores_visible();
+    }
+
+    // ---- forward: the sequences, if the block fits ----
+    auto put = [&](uint32_t at, uint32_t v) {   // one output byte
+        if (lane == 0) dst[at] = (uint8_t)v;
+    };
+    auto put_len = [&](uint32_t at, uint32_t v, uint32_t nb) {   // a length field's nb bytes
+        for (uint32_t j = (uint32_t)lane; j < nb; j += 64u)
+            dst[at + j] = (uint8_t)(j + 1u == nb ? (v - 15u) % 255u : 255u);
+    };
+    auto copy = [&](uint32_t at, uint32_t s, uint32_t len) {     // literals
+        for (uint32_t j = 16u * (uint32_t)lane; j + 16u <= len; j += 1024u)
+            gstore16(dst + at + j, gload16(src + s + j));
+        const uint32_t r = len & ~15u;
+        if ((uint32_t)lane < len - r) dst[at + r + lane] = src[s + r + lane];
+    };
+
+    const bool fit = total <= ucap;   // decided before anything is written
+    uint32_t op = 0u, anchor = 0u;
+    bool fail = !fit;
+    if (fit && n >= kMinLength) {
+        uint32_t p = 0u;
+        while (p <= last) {
+            // 64 positions from p: the first one with a choice (below 4: none, so p advances)
+            const uint32_t pos = p + (uint32_t)lane;
+            const uint32_t c = pos <= last ? M[pos] : 0u;
+            const uint64_t has = wave_ballot((c >> 16) >= (uint32_t)kMinMatch);
+            if (!has) {
+                p += 64u;
+                continue;
+            }
+            const int fl = __builtin_ctzll(has);
+            const uint32_t sp = p + (uint32_t)fl, mm = lane_val(c, fl);
+            const uint32_t q = mm & 0xFFFFu, L = umin(mm >> 16, end - sp);
+            const uint32_t lits = sp - anchor, ml = L - (uint32_t)kMinMatch, off = uD + sp - q;
+            const uint32_t nlb = opt_len_bytes(lits), nmb = opt_len_bytes(ml);
+            if (op + 1u + nlb + lits + 2u + nmb > ucap) {   // (the sequences sum to cost[0])
+                fail = true;
+                break;
+            }
+            put(op, umin(lits, 15u) << 4 | umin(ml, 15u));
+            op += 1u;
+            put_len(op, lits, nlb);
+            op += nlb;
+            copy(op, anchor, lits);
+            op += lits;
+            put(op, off & 255u);
+            put(op + 1u, off >> 8);
+            op += 2u;
+            put_len(op, ml, nmb);
+            op += nmb;
+            p = sp + L;
+            anchor = p;
+        }
+    }
+    int result = 0;
+    if (!fail) {
+        const uint32_t run = un - anchor, nlb = opt_len_bytes(run);
+        if (op + 1u + nlb + run <= ucap) {
+            put(op, umin(run, 15u) << 4);
+            op += 1u;
+            put_len(op, run, nlb);
+            op += nlb;
+            copy(op, anchor, run);
+            result = (int)(op + run);
+        }
+    }
+    if (lane == 0) a.result[b] = result;
+}
+
 }  // namespace
 
 hipError_t launch_hc_cdict_prepare(const char *dict, int dict_size, int max_src, void *cdict,
@@ -367,6 +608,17 @@ hipError_t launch_encode_hc_cdict(const HcDictArgs &a, hipStream_t s) {
     hipLaunchKernelGGL(lz4_hc_cdict_search_kernel, dim3((unsigned)a.nblocks * groups),
                        dim3(kHcdThreads), 0, s, a, groups);
     hipLaunchKernelGGL(lz4_hc_cdict_parse_kernel, dim3(a.nblocks), dim3(64), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_encode_hc_cdict_opt(const HcDictOptArgs &o, hipStream_t s) {
+    const HcDictArgs &a = o.a;
+    if (a.nblocks <= 0) return hipSuccess;
+    const int groups = hc_cdict_groups(a.max_src);
+    hipLaunchKernelGGL(lz4_hc_cdict_chain_kernel, dim3(a.nblocks), dim3(64), 0, s, a);
+    hipLaunchKernelGGL(lz4_hc_cdict_search_kernel, dim3((unsigned)a.nblocks * groups),
+                       dim3(kHcdThreads), 0, s, a, groups);
+    hipLaunchKernelGGL(lz4_hc_cdict_opt_parse_kernel, dim3(a.nblocks), dim3(64), 0, s, o);
     return hipGetLastError();
 }
 

@@ -650,20 +650,29 @@ size_t APE_LZ4_compress_hc_usingCDict_scratch_size(int nblocks, int maxSrcSize) 
     return (size_t)(nblocks < sub ? nblocks : sub) * hc_cdict_slot_bytes(maxSrcSize);
 }
 
-int APE_LZ4_compress_hc_usingCDict_batch_dev(const char *const *d_src, const int *d_srcSize,
-                                             char *const *d_dst, const int *d_dstCap,
-                                             int *d_result, int nblocks, const void *d_cdict,
-                                             int maxSrcSize, int depth, void *d_scratch,
-                                             size_t scratch_bytes, void *stream) {
+size_t APE_LZ4_compress_hc_opt_usingCDict_scratch_size(int nblocks, int maxSrcSize) {
+    if (nblocks <= 0 || maxSrcSize < 1 || maxSrcSize > kMaxBlock) return 0;
+    const int sub = hc_cdict_sub(maxSrcSize);
+    return (size_t)(nblocks < sub ? nblocks : sub) * hc_cdict_opt_slot_bytes(maxSrcSize);
+}
+
+namespace {
+// opt: the cost-minimising parse (lz4_hc_cdict_opt_parse_kernel), whose cost tables follow the
+// match tables in the scratch
+int hc_cdict_batch(const char *what, bool opt, const char *const *d_src, const int *d_srcSize,
+                   char *const *d_dst, const int *d_dstCap, int *d_result, int nblocks,
+                   const void *d_cdict, int maxSrcSize, int depth, void *d_scratch,
+                   size_t scratch_bytes, void *stream) {
     const bool range = maxSrcSize >= 1 && maxSrcSize <= kMaxBlock;
-    const size_t slot = range ? hc_cdict_slot_bytes(maxSrcSize) : 0;
+    const size_t slot = !range ? 0 : opt ? hc_cdict_opt_slot_bytes(maxSrcSize)
+                                         : hc_cdict_slot_bytes(maxSrcSize);
     if (nblocks < 0 || !range || depth < 0 || depth > kHcMaxDepth || !d_cdict ||
         ((uintptr_t)d_cdict & 15u) || !d_scratch || ((uintptr_t)d_scratch & 15u) ||
         scratch_bytes < slot ||
         (nblocks > 0 && (!d_src || !d_srcSize || !d_dst || !d_dstCap || !d_result))) {
-        snprintf(g_err, sizeof g_err, "compress_hc_usingCDict: nblocks %d, maxSrcSize %d (1..%d), "
+        snprintf(g_err, sizeof g_err, "%s: nblocks %d, maxSrcSize %d (1..%d), "
                  "depth %d (0..%d), object at %p, scratch of %zu bytes at %p (need %zu bytes; "
-                 "both 16-byte aligned)", nblocks, maxSrcSize, kMaxBlock, depth, kHcMaxDepth,
+                 "both 16-byte aligned)", what, nblocks, maxSrcSize, kMaxBlock, depth, kHcMaxDepth,
                  d_cdict, scratch_bytes, d_scratch, slot);
         return APE_LZ4_GPU_EINVAL;
     }
@@ -690,10 +699,41 @@ int APE_LZ4_compress_hc_usingCDict_batch_dev(const char *const *d_src, const int
         a.match_stride = (uint32_t)hc_cdict_match_entries(maxSrcSize);
         a.chain = (uint16_t *)d_scratch;
         a.match = (uint32_t *)((char *)d_scratch + (size_t)sub * a.chain_stride * sizeof(uint16_t));
-        e = launch_encode_hc_cdict(a, (hipStream_t)stream);
+        if (opt) {
+            HcDictOptArgs o{};
+            o.a = a;
+            o.cost_stride = (uint32_t)hc_cdict_cost_entries(maxSrcSize);
+            o.cost = (uint32_t *)((char *)d_scratch + (size_t)sub * hc_cdict_slot_bytes(maxSrcSize));
+            e = launch_encode_hc_cdict_opt(o, (hipStream_t)stream);
+        } else {
+            e = launch_encode_hc_cdict(a, (hipStream_t)stream);
+        }
     }
-    return finish_launch(e, "lz4_hc_cdict_chain_kernel + lz4_hc_cdict_search_kernel + "
-                            "lz4_hc_cdict_parse_kernel");
+    return finish_launch(e, opt ? "lz4_hc_cdict_chain_kernel + lz4_hc_cdict_search_kernel + "
+                                  "lz4_hc_cdict_opt_parse_kernel"
+                                : "lz4_hc_cdict_chain_kernel + lz4_hc_cdict_search_kernel + "
+                                  "lz4_hc_cdict_parse_kernel");
+}
+}  // namespace
+
+int APE_LZ4_compress_hc_usingCDict_batch_dev(const char *const *d_src, const int *d_srcSize,
+                                             char *const *d_dst, const int *d_dstCap,
+                                             int *d_result, int nblocks, const void *d_cdict,
+                                             int maxSrcSize, int depth, void *d_scratch,
+                                             size_t scratch_bytes, void *stream) {
+    return hc_cdict_batch("compress_hc_usingCDict", false, d_src, d_srcSize, d_dst, d_dstCap,
+                          d_result, nblocks, d_cdict, maxSrcSize, depth, d_scratch, scratch_bytes,
+                          stream);
+}
+
+int APE_LZ4_compress_hc_opt_usingCDict_batch_dev(const char *const *d_src, const int *d_srcSize,
+                                                 char *const *d_dst, const int *d_dstCap,
+                                                 int *d_result, int nblocks, const void *d_cdict,
+                                                 int maxSrcSize, int depth, void *d_scratch,
+                                                 size_t scratch_bytes, void *stream) {
+    return hc_cdict_batch("compress_hc_opt_usingCDict", true, d_src, d_srcSize, d_dst, d_dstCap,
+                          d_result, nblocks, d_cdict, maxSrcSize, depth, d_scratch, scratch_bytes,
+                          stream);
 }
 
 // ---- inputs of any size as one block (lz4_large.hip) ----
