@@ -255,7 +255,7 @@ int APE_LZ4_compress_hc_withPrefix_batch_dev(const char *const *d_src, const int
                                              int depth, void *d_scratch, size_t scratch_bytes,
                                              void *stream);
 
-/* ---- high-ratio mode, cost-minimising parse (lz4_encode_hc_opt.hip) ----
+/* ---- high-ratio mode, cost-minimising parse (lz4_encode_hc.hip) ----
  * APE_LZ4_compress_hc_opt_batch_dev and APE_LZ4_compress_hc_opt_withPrefix_batch_dev are the two
  * calls above with another parse over the same search: arguments, used history, depth (0..256,
  * 0 = 64), per-block results, what is read and written, passes and errors are theirs.  THE RULE:

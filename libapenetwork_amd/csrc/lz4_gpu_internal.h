@@ -250,7 +250,7 @@ struct HcArgs {
 // chain build (one wave per block), search (one lane per position), parse + emit (one wave per
 // block)
 hipError_t launch_encode_hc(const HcArgs &a, hipStream_t s, hipEvent_t *ev = nullptr);
-// The cost-minimising parse (lz4_encode_hc_opt.hip; tests/hcoptmodel.py is the
+// The cost-minimising parse (lz4_encode_hc.hip; tests/hcoptmodel.py is the
 // definition): the chain build and the search above as they are, then a parse that prices
 // every position backward and emits forward.  It needs one more table per block, cost[p] (u32:
 // the bytes the rest of the block takes from p on), so the scratch of one block is

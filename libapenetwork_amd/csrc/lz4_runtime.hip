@@ -531,7 +531,7 @@ size_t APE_LZ4_compress_hc_opt_scratch_size(int nblocks) {
 
 namespace {
 // d_prefixSize (nullable): per-block bytes of history before d_src[i]; opt: the cost-minimising
-// parse (lz4_encode_hc_opt.hip), whose cost tables follow the match tables in the scratch
+// parse (lz4_encode_hc.hip), whose cost tables follow the match tables in the scratch
 int hc_batch(const char *what, bool opt, const char *const *d_src, const int *d_srcSize,
              const int *d_prefixSize, char *const *d_dst, const int *d_dstCap, int *d_result,
              int nblocks, int depth, void *d_scratch, size_t scratch_bytes, void *stream) {
