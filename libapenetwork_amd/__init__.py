@@ -70,6 +70,7 @@ def lib():
             "APE_LZ4_gpu_init": (i, []),
             "APE_LZ4_gpu_device_count": (i, []),
             "APE_LZ4_gpu_last_error": (cp, []),
+            "APE_LZ4_gpu_arch": (cp, []),
             "APE_LZ4_gpu_set_oneshot_host_below": (i, [i]),
             "APE_LZ4_compress_batch_dev": (i, [p, p, p, p, p, i, p]),
             "APE_LZ4_compress_fast_batch_dev": (i, [p, p, p, p, p, i, i, p]),
@@ -82,6 +83,8 @@ def lib():
             "APE_LZ4_decompress_safe_partial_batch_dev": (i, [p, p, p, p, p, p, i, p]),
             "APE_LZ4_compress_batch_strided_dev": (i, [p, sz, p, p, sz, p, p, i, p]),
             "APE_LZ4_decompress_safe_batch_strided_dev": (i, [p, sz, p, p, sz, p, p, i, p]),
+            "APE_LZ4_compress_batch_host": (i, [p, p, p, p, p, i]),
+            "APE_LZ4_decompress_safe_batch_host": (i, [p, p, p, p, p, i]),
             "APE_LZ4_synth_blocks_dev": (i, [p, sz, i, ll, i, i, p]),
             "APE_LZ4_frame_scratch_size": (sz, [i]),
             "APE_LZ4_frame_offsets_dev": (i, [p, p, p, i, p]),
@@ -92,6 +95,7 @@ def lib():
             "APE_LZ4_compress_large_slice_size": (i, []),
             "APE_LZ4_compress_large_scratch_size": (sz, [i, i]),
             "APE_LZ4_compress_large_batch_dev": (i, [p, p, p, p, p, i, i, i, p, sz, p]),
+            "APE_LZ4_compress_large_timed_dev": (i, [p, p, p, p, p, i, i, i, p, sz, p, p]),
             "APE_LZ4_large_index_segments": (i, [i, i]),
             "APE_LZ4_large_index_size": (sz, [i, i]),
             "APE_LZ4_compress_large_indexed_batch_dev": (i, [p, p, p, p, p, i, i, i, p, sz, i, p, sz, p]),
@@ -289,23 +293,60 @@ def _strided_args(src, sizes, dst, results, caps, what):
     return n
 
 
-def _ptr_args(what, n, **arrs):
-    """Pointer-array calls: name -> (tensor, dtype) of N elements each (int64 pointers, int32
-    sizes); a None tensor is allowed where dtype is given as (dtype, True)."""
-    for name, (t, spec) in arrs.items():
-        dtype, opt = spec if isinstance(spec, tuple) else (spec, False)
-        _arr(t, "%s %s" % (what, name), dtype, n, optional=opt, cuda=False)
-    _on_cuda(what, *(t for t, _ in arrs.values()))
-
-
-def _i64():
+def _ptr_args(what, n, optional=(), **arrs):
+    """Pointer-array calls: name -> tensor of n elements each, int64 where the name ends in
+    _ptrs (pointers), int32 otherwise (sizes); the names in `optional` may be None."""
     import torch
-    return torch.int64
+    for name, t in arrs.items():
+        _arr(t, "%s %s" % (what, name), torch.int64 if name.endswith("_ptrs") else torch.int32, n,
+             optional=name in optional, cuda=False)
+    _on_cuda(what, *arrs.values())
 
 
-def _i32():
+def _count(what, name, sizes):
+    """The length of a batch, from its int32 sizes tensor -- validated before its shape is
+    read, so anything else is a ValueError."""
     import torch
-    return torch.int32
+    _arr(sizes, "%s %s" % (what, name), torch.int32, cuda=False)
+    return sizes.shape[0]
+
+
+_FIVE = "src_ptrs src_sizes dst_ptrs caps results"
+
+
+def _ptr_batch(what, names, src_ptrs, sizes, dst_ptrs, caps, results, optional=(), **more):
+    """The pointer-array form: the sizes tensor first, since it gives the batch its length,
+    then the standard five tensors (called `names` in messages) and any further per-block
+    tensors in `more`, as _ptr_args takes them.  Returns the number of blocks."""
+    names = names.split()
+    n = _count(what, names[1], sizes)
+    _ptr_args(what, n, optional, **dict(zip(names, (src_ptrs, sizes, dst_ptrs, caps, results))),
+              **more)
+    return n
+
+
+def _bytes(t, what):
+    """A scratch, a prepared dictionary, a dictionary: a contiguous uint8 CUDA tensor."""
+    import torch
+    _arr(t, what, torch.uint8)
+
+
+def _large_scratch(what, scratch, like, size_fn, *size_args):
+    """The caller's scratch, validated, or a new one of size_fn(*size_args) bytes on the
+    device of `like`."""
+    if scratch is not None:
+        _bytes(scratch, what + " scratch")
+        return scratch
+    import torch
+    need = size_fn(*size_args)
+    if need == 0 or need >= 1 << 63:
+        raise ValueError("%s: max_src_size outside [1, 0x7E000000] or too many slices for one "
+                         "call" % what)
+    return torch.empty(need, dtype=torch.uint8, device=like.device)
+
+
+def _call(symbol, *args):
+    _check(getattr(lib(), symbol)(*args), symbol)
 
 
 def compress_batch(src, src_sizes, dst, results, dst_caps=None, stream=None):
@@ -315,80 +356,66 @@ def compress_batch(src, src_sizes, dst, results, dst_caps=None, stream=None):
     dst: uint8 [N, D] CUDA tensor; results: int32 [N] (compressed size or 0).
     """
     n = _strided_args(src, src_sizes, dst, results, dst_caps, "compress_batch")
-    _check(lib().APE_LZ4_compress_batch_strided_dev(
-        _ptr(src), src.stride(0), _ptr(src_sizes), _ptr(dst), dst.stride(0), _ptr(dst_caps),
-        _ptr(results), n, _stream(stream)), "APE_LZ4_compress_batch_strided_dev")
+    _call("APE_LZ4_compress_batch_strided_dev", _ptr(src), src.stride(0), _ptr(src_sizes),
+          _ptr(dst), dst.stride(0), _ptr(dst_caps), _ptr(results), n, _stream(stream))
 
 
 def decompress_batch(comp, comp_sizes, dst, results, dst_caps=None, stream=None):
     """N x APE_LZ4_decompress_safe on device (caps default to dst row stride)."""
     n = _strided_args(comp, comp_sizes, dst, results, dst_caps, "decompress_batch")
-    _check(lib().APE_LZ4_decompress_safe_batch_strided_dev(
-        _ptr(comp), comp.stride(0), _ptr(comp_sizes), _ptr(dst), dst.stride(0), _ptr(dst_caps),
-        _ptr(results), n, _stream(stream)), "APE_LZ4_decompress_safe_batch_strided_dev")
+    _call("APE_LZ4_decompress_safe_batch_strided_dev", _ptr(comp), comp.stride(0),
+          _ptr(comp_sizes), _ptr(dst), dst.stride(0), _ptr(dst_caps), _ptr(results), n,
+          _stream(stream))
 
 
 def decompress_partial_batch(src_ptrs, comp_sizes, dst_ptrs, targets, caps, results,
                              stream=None):
     """N x APE_LZ4_decompress_safe_partial, pointer-array form (int64 tensors of pointers)."""
-    n = comp_sizes.shape[0]
-    _ptr_args("decompress_partial_batch", n, src_ptrs=(src_ptrs, _i64()), comp_sizes=(comp_sizes, _i32()),
-              dst_ptrs=(dst_ptrs, _i64()), targets=(targets, _i32()), caps=(caps, _i32()),
-              results=(results, _i32()))
-    _check(lib().APE_LZ4_decompress_safe_partial_batch_dev(
-        _ptr(src_ptrs), _ptr(comp_sizes), _ptr(dst_ptrs), _ptr(targets), _ptr(caps),
-        _ptr(results), n, _stream(stream)), "APE_LZ4_decompress_safe_partial_batch_dev")
+    n = _ptr_batch("decompress_partial_batch", "src_ptrs comp_sizes dst_ptrs caps results",
+                   src_ptrs, comp_sizes, dst_ptrs, caps, results, targets=targets)
+    _call("APE_LZ4_decompress_safe_partial_batch_dev", _ptr(src_ptrs), _ptr(comp_sizes),
+          _ptr(dst_ptrs), _ptr(targets), _ptr(caps), _ptr(results), n, _stream(stream))
 
 
 def compress_fast_ptr_batch(src_ptrs, src_sizes, dst_ptrs, caps, results, acceleration,
                             stream=None):
     """N x APE_LZ4_compress_fast, pointer-array form (int64 tensors of pointers)."""
-    n = src_sizes.shape[0]
-    _ptr_args("compress_fast_ptr_batch", n, src_ptrs=(src_ptrs, _i64()), src_sizes=(src_sizes, _i32()),
-              dst_ptrs=(dst_ptrs, _i64()), caps=(caps, _i32()), results=(results, _i32()))
-    _check(lib().APE_LZ4_compress_fast_batch_dev(
-        _ptr(src_ptrs), _ptr(src_sizes), _ptr(dst_ptrs), _ptr(caps), _ptr(results), n,
-        acceleration, _stream(stream)), "APE_LZ4_compress_fast_batch_dev")
+    n = _ptr_batch("compress_fast_ptr_batch", _FIVE, src_ptrs, src_sizes, dst_ptrs, caps, results)
+    _call("APE_LZ4_compress_fast_batch_dev", _ptr(src_ptrs), _ptr(src_sizes), _ptr(dst_ptrs),
+          _ptr(caps), _ptr(results), n, acceleration, _stream(stream))
 
 
 def compress_exact_ptr_batch(src_ptrs, src_sizes, dst_ptrs, caps, results, acceleration=1,
                              stream=None):
     """Greedy-exact mode: N x APE_LZ4_compress_fast byte for byte (the reference's own
     sequential parse, one wave per block; slow, for debugging)."""
-    n = src_sizes.shape[0]
-    _ptr_args("compress_exact_ptr_batch", n, src_ptrs=(src_ptrs, _i64()), src_sizes=(src_sizes, _i32()),
-              dst_ptrs=(dst_ptrs, _i64()), caps=(caps, _i32()), results=(results, _i32()))
-    _check(lib().APE_LZ4_compress_exact_batch_dev(
-        _ptr(src_ptrs), _ptr(src_sizes), _ptr(dst_ptrs), _ptr(caps), _ptr(results), n,
-        acceleration, _stream(stream)), "APE_LZ4_compress_exact_batch_dev")
+    n = _ptr_batch("compress_exact_ptr_batch", _FIVE, src_ptrs, src_sizes, dst_ptrs, caps, results)
+    _call("APE_LZ4_compress_exact_batch_dev", _ptr(src_ptrs), _ptr(src_sizes), _ptr(dst_ptrs),
+          _ptr(caps), _ptr(results), n, acceleration, _stream(stream))
+
+
+_DESTSIZE = "src_ptrs src_sizes dst_ptrs targets results"
 
 
 def compress_destSize_ptr_batch(src_ptrs, src_sizes, dst_ptrs, targets, results, stream=None):
     """N x APE_LZ4_compress_destSize, pointer-array form: src_sizes (int32) is in/out --
     input sizes on entry, consumed input bytes on return; results = bytes written."""
-    n = src_sizes.shape[0]
-    _ptr_args("compress_destSize_ptr_batch", n, src_ptrs=(src_ptrs, _i64()),
-              src_sizes=(src_sizes, _i32()), dst_ptrs=(dst_ptrs, _i64()), targets=(targets, _i32()),
-              results=(results, _i32()))
-    _check(lib().APE_LZ4_compress_destSize_batch_dev(
-        _ptr(src_ptrs), _ptr(src_sizes), _ptr(dst_ptrs), _ptr(targets), _ptr(results), n,
-        _stream(stream)), "APE_LZ4_compress_destSize_batch_dev")
+    n = _ptr_batch("compress_destSize_ptr_batch", _DESTSIZE, src_ptrs, src_sizes, dst_ptrs,
+                   targets, results)
+    _call("APE_LZ4_compress_destSize_batch_dev", _ptr(src_ptrs), _ptr(src_sizes), _ptr(dst_ptrs),
+          _ptr(targets), _ptr(results), n, _stream(stream))
 
 
 def compress_destSize_scratch_ptr_batch(src_ptrs, src_sizes, dst_ptrs, targets, results,
                                         scratch, stream=None):
     """compress_destSize_ptr_batch with caller-owned scratch (uint8 CUDA tensor of at least
     destSize_scratch_size(1) bytes): allocates nothing, so it can be graph-captured."""
-    n = src_sizes.shape[0]
-    _ptr_args("compress_destSize_scratch_ptr_batch", n, src_ptrs=(src_ptrs, _i64()),
-              src_sizes=(src_sizes, _i32()), dst_ptrs=(dst_ptrs, _i64()), targets=(targets, _i32()),
-              results=(results, _i32()))
-    import torch
-    _arr(scratch, "compress_destSize_scratch_ptr_batch scratch", torch.uint8)
-    _check(lib().APE_LZ4_compress_destSize_batch_scratch_dev(
-        _ptr(src_ptrs), _ptr(src_sizes), _ptr(dst_ptrs), _ptr(targets), _ptr(results), n,
-        _ptr(scratch), scratch.numel(), _stream(stream)),
-        "APE_LZ4_compress_destSize_batch_scratch_dev")
+    what = "compress_destSize_scratch_ptr_batch"
+    n = _ptr_batch(what, _DESTSIZE, src_ptrs, src_sizes, dst_ptrs, targets, results)
+    _bytes(scratch, what + " scratch")
+    _call("APE_LZ4_compress_destSize_batch_scratch_dev", _ptr(src_ptrs), _ptr(src_sizes),
+          _ptr(dst_ptrs), _ptr(targets), _ptr(results), n, _ptr(scratch), scratch.numel(),
+          _stream(stream))
 
 
 def destSize_scratch_size(nblocks):
@@ -398,36 +425,31 @@ def destSize_scratch_size(nblocks):
 def decompress_fast_ptr_batch(src_ptrs, src_bounds, dst_ptrs, original_sizes, results,
                               stream=None):
     """N x APE_LZ4_decompress_fast, pointer-array form: results = input bytes consumed."""
-    n = original_sizes.shape[0]
-    _ptr_args("decompress_fast_ptr_batch", n, src_ptrs=(src_ptrs, _i64()),
-              src_bounds=(src_bounds, _i32()), dst_ptrs=(dst_ptrs, _i64()),
-              original_sizes=(original_sizes, _i32()), results=(results, _i32()))
-    _check(lib().APE_LZ4_decompress_fast_batch_dev(
-        _ptr(src_ptrs), _ptr(src_bounds), _ptr(dst_ptrs), _ptr(original_sizes), _ptr(results),
-        n, _stream(stream)), "APE_LZ4_decompress_fast_batch_dev")
+    n = _ptr_batch("decompress_fast_ptr_batch",
+                   "src_ptrs src_bounds dst_ptrs original_sizes results", src_ptrs, src_bounds,
+                   dst_ptrs, original_sizes, results)
+    _call("APE_LZ4_decompress_fast_batch_dev", _ptr(src_ptrs), _ptr(src_bounds), _ptr(dst_ptrs),
+          _ptr(original_sizes), _ptr(results), n, _stream(stream))
+
+
+_DECODE = "src_ptrs comp_sizes dst_ptrs caps results"
 
 
 def decompress_ptr_batch(src_ptrs, comp_sizes, dst_ptrs, caps, results, stream=None):
     """N x APE_LZ4_decompress_safe, pointer-array form."""
-    n = comp_sizes.shape[0]
-    _ptr_args("decompress_ptr_batch", n, src_ptrs=(src_ptrs, _i64()), comp_sizes=(comp_sizes, _i32()),
-              dst_ptrs=(dst_ptrs, _i64()), caps=(caps, _i32()), results=(results, _i32()))
-    _check(lib().APE_LZ4_decompress_safe_batch_dev(
-        _ptr(src_ptrs), _ptr(comp_sizes), _ptr(dst_ptrs), _ptr(caps), _ptr(results), n,
-        _stream(stream)), "APE_LZ4_decompress_safe_batch_dev")
+    n = _ptr_batch("decompress_ptr_batch", _DECODE, src_ptrs, comp_sizes, dst_ptrs, caps, results)
+    _call("APE_LZ4_decompress_safe_batch_dev", _ptr(src_ptrs), _ptr(comp_sizes), _ptr(dst_ptrs),
+          _ptr(caps), _ptr(results), n, _stream(stream))
 
 
 def compress_prefix_batch(src_ptrs, src_sizes, prefix_sizes, dst_ptrs, caps, results,
                           stream=None):
     """N chained-stream chunks (compress_fast_continue on a stream whose history is the
     prefix_sizes[i] bytes just before src_ptrs[i]); pointer-array form (int64 tensors)."""
-    n = src_sizes.shape[0]
-    _ptr_args("compress_prefix_batch", n, src_ptrs=(src_ptrs, _i64()), src_sizes=(src_sizes, _i32()),
-              prefix_sizes=(prefix_sizes, _i32()), dst_ptrs=(dst_ptrs, _i64()),
-              caps=(caps, _i32()), results=(results, _i32()))
-    _check(lib().APE_LZ4_compress_withPrefix_batch_dev(
-        _ptr(src_ptrs), _ptr(src_sizes), _ptr(prefix_sizes), _ptr(dst_ptrs), _ptr(caps),
-        _ptr(results), n, _stream(stream)), "APE_LZ4_compress_withPrefix_batch_dev")
+    n = _ptr_batch("compress_prefix_batch", _FIVE, src_ptrs, src_sizes, dst_ptrs, caps, results,
+                   prefix_sizes=prefix_sizes)
+    _call("APE_LZ4_compress_withPrefix_batch_dev", _ptr(src_ptrs), _ptr(src_sizes),
+          _ptr(prefix_sizes), _ptr(dst_ptrs), _ptr(caps), _ptr(results), n, _stream(stream))
 
 
 def compress_large_slice_size():
@@ -446,23 +468,13 @@ def compress_large_ptr_batch(src_ptrs, src_sizes, dst_ptrs, caps, results, max_s
     block (slices compressed in parallel, then stitched); pointer-array form (int64 tensors of
     pointers).  scratch: uint8 CUDA tensor of at least compress_large_scratch_size(N,
     max_src_size) bytes, 16-byte aligned; None allocates one.  Returns the scratch."""
-    import torch
-    _arr(src_sizes, "compress_large_ptr_batch src_sizes", torch.int32)
-    n = src_sizes.shape[0]
-    _ptr_args("compress_large_ptr_batch", n, src_ptrs=(src_ptrs, _i64()), src_sizes=(src_sizes, _i32()),
-              dst_ptrs=(dst_ptrs, _i64()), caps=(caps, _i32()), results=(results, _i32()))
-    if scratch is None:
-        need = compress_large_scratch_size(n, max_src_size)
-        if need == 0 or need >= 1 << 63:
-            raise ValueError("compress_large_ptr_batch: max_src_size outside [1, 0x7E000000] "
-                             "or too many slices for one call")
-        scratch = torch.empty(need, dtype=torch.uint8, device=src_sizes.device)
-    else:
-        _arr(scratch, "compress_large_ptr_batch scratch", torch.uint8)
-    _check(lib().APE_LZ4_compress_large_batch_dev(
-        _ptr(src_ptrs), _ptr(src_sizes), _ptr(dst_ptrs), _ptr(caps), _ptr(results), n,
-        max_src_size, acceleration, _ptr(scratch), scratch.numel(), _stream(stream)),
-        "APE_LZ4_compress_large_batch_dev")
+    what = "compress_large_ptr_batch"
+    n = _ptr_batch(what, _FIVE, src_ptrs, src_sizes, dst_ptrs, caps, results)
+    scratch = _large_scratch(what, scratch, src_sizes, compress_large_scratch_size, n,
+                             max_src_size)
+    _call("APE_LZ4_compress_large_batch_dev", _ptr(src_ptrs), _ptr(src_sizes), _ptr(dst_ptrs),
+          _ptr(caps), _ptr(results), n, max_src_size, acceleration, _ptr(scratch),
+          scratch.numel(), _stream(stream))
     return scratch
 
 
@@ -477,9 +489,11 @@ def large_index_size(max_src_size, restart_bytes):
     return lib().APE_LZ4_large_index_size(max_src_size, restart_bytes)
 
 
-def _index_arg(what, index, n):
+def _index_arg(what, index, n, optional=False):
     """The seek indexes of n blocks: a 2-D uint8 CUDA tensor [n, stride] (16-byte alignment
-    and the stride are checked by the C side)."""
+    and the stride are checked by the C side).  Returns the stride (0 without an index)."""
+    if index is None and optional:
+        return 0
     _rows(index, what + " index", n)
     return index.stride(0) if n > 1 else index.shape[1]
 
@@ -490,27 +504,14 @@ def compress_large_indexed_ptr_batch(src_ptrs, src_sizes, dst_ptrs, caps, result
     """compress_large_ptr_batch with a restart point every restart_bytes (0 or a multiple of the
     slice size), and, when index (uint8 CUDA [N, stride >= large_index_size(max_src_size,
     restart_bytes)]) is given, each block's seek index in its row.  Returns the scratch."""
-    import torch
-    _arr(src_sizes, "compress_large_indexed_ptr_batch src_sizes", torch.int32)
-    n = src_sizes.shape[0]
-    _ptr_args("compress_large_indexed_ptr_batch", n, src_ptrs=(src_ptrs, _i64()),
-              src_sizes=(src_sizes, _i32()), dst_ptrs=(dst_ptrs, _i64()), caps=(caps, _i32()),
-              results=(results, _i32()))
-    stride = 0
-    if index is not None:
-        stride = _index_arg("compress_large_indexed_ptr_batch", index, n)
-    if scratch is None:
-        need = compress_large_scratch_size(n, max_src_size)
-        if need == 0 or need >= 1 << 63:
-            raise ValueError("compress_large_indexed_ptr_batch: max_src_size outside "
-                             "[1, 0x7E000000] or too many slices for one call")
-        scratch = torch.empty(need, dtype=torch.uint8, device=src_sizes.device)
-    else:
-        _arr(scratch, "compress_large_indexed_ptr_batch scratch", torch.uint8)
-    _check(lib().APE_LZ4_compress_large_indexed_batch_dev(
-        _ptr(src_ptrs), _ptr(src_sizes), _ptr(dst_ptrs), _ptr(caps), _ptr(results), n,
-        max_src_size, acceleration, _ptr(scratch), scratch.numel(), restart_bytes, _ptr(index),
-        stride, _stream(stream)), "APE_LZ4_compress_large_indexed_batch_dev")
+    what = "compress_large_indexed_ptr_batch"
+    n = _ptr_batch(what, _FIVE, src_ptrs, src_sizes, dst_ptrs, caps, results)
+    stride = _index_arg(what, index, n, optional=True)
+    scratch = _large_scratch(what, scratch, src_sizes, compress_large_scratch_size, n,
+                             max_src_size)
+    _call("APE_LZ4_compress_large_indexed_batch_dev", _ptr(src_ptrs), _ptr(src_sizes),
+          _ptr(dst_ptrs), _ptr(caps), _ptr(results), n, max_src_size, acceleration, _ptr(scratch),
+          scratch.numel(), restart_bytes, _ptr(index), stride, _stream(stream))
     return scratch
 
 
@@ -519,17 +520,12 @@ def decompress_indexed_ptr_batch(src_ptrs, comp_sizes, dst_ptrs, caps, index, ma
     """N x APE_LZ4_decompress_safe on blocks with a seek index (uint8 CUDA [N, stride], as
     compress_large_indexed_ptr_batch wrote it), one wave per segment; a block with more than
     max_segments segments gets ERANGE.  Pointer-array form."""
-    import torch
-    _arr(comp_sizes, "decompress_indexed_ptr_batch comp_sizes", torch.int32)
-    n = comp_sizes.shape[0]
-    _ptr_args("decompress_indexed_ptr_batch", n, src_ptrs=(src_ptrs, _i64()),
-              comp_sizes=(comp_sizes, _i32()), dst_ptrs=(dst_ptrs, _i64()), caps=(caps, _i32()),
-              results=(results, _i32()))
-    stride = _index_arg("decompress_indexed_ptr_batch", index, n)
-    _check(lib().APE_LZ4_decompress_safe_indexed_batch_dev(
-        _ptr(src_ptrs), _ptr(comp_sizes), _ptr(dst_ptrs), _ptr(caps), _ptr(index), stride,
-        max_segments, _ptr(results), n, _stream(stream)),
-        "APE_LZ4_decompress_safe_indexed_batch_dev")
+    what = "decompress_indexed_ptr_batch"
+    n = _ptr_batch(what, _DECODE, src_ptrs, comp_sizes, dst_ptrs, caps, results)
+    stride = _index_arg(what, index, n)
+    _call("APE_LZ4_decompress_safe_indexed_batch_dev", _ptr(src_ptrs), _ptr(comp_sizes),
+          _ptr(dst_ptrs), _ptr(caps), _ptr(index), stride, max_segments, _ptr(results), n,
+          _stream(stream))
 
 
 def decompress_range_indexed_ptr_batch(src_ptrs, comp_sizes, index, max_segments, range_starts,
@@ -542,24 +538,20 @@ def decompress_range_indexed_ptr_batch(src_ptrs, comp_sizes, index, max_segments
     request; window is int32 [2 * requests] and receives {where the range begins in dst, the
     bytes of dst used}; results the bytes read, or a negative code (ERANGE: caps[r] is below
     window[2r + 1])."""
-    import torch
     what = "decompress_range_indexed_ptr_batch"
-    _arr(comp_sizes, what + " comp_sizes", torch.int32)
-    _arr(range_starts, what + " range_starts", torch.int32)
-    nb, nreq = comp_sizes.shape[0], range_starts.shape[0]
-    _ptr_args(what, nb, src_ptrs=(src_ptrs, _i64()), comp_sizes=(comp_sizes, _i32()))
-    _ptr_args(what, nreq, range_starts=(range_starts, _i32()), range_lens=(range_lens, _i32()),
-              dst_ptrs=(dst_ptrs, _i64()), caps=(caps, _i32()), results=(results, _i32()),
-              block_of=(block_of, (_i32(), True)))
-    _arr(window, what + " window", torch.int32, 2 * nreq)
+    nb = _count(what, "comp_sizes", comp_sizes)
+    nreq = _count(what, "range_starts", range_starts)
+    _ptr_args(what, nb, src_ptrs=src_ptrs, comp_sizes=comp_sizes)
+    _ptr_args(what, nreq, ("block_of",), range_starts=range_starts, range_lens=range_lens,
+              dst_ptrs=dst_ptrs, caps=caps, results=results, block_of=block_of)
+    _ptr_args(what, 2 * nreq, window=window)
     if block_of is None and nreq != nb:
         raise ValueError("%s: %d requests for %d blocks need block_of" % (what, nreq, nb))
     stride = _index_arg(what, index, nb)
-    _check(lib().APE_LZ4_decompress_range_indexed_batch_dev(
-        _ptr(src_ptrs), _ptr(comp_sizes), _ptr(index), stride, max_segments, nb, _ptr(block_of),
-        _ptr(range_starts), _ptr(range_lens), _ptr(dst_ptrs), _ptr(caps), _ptr(window),
-        _ptr(results), nreq, waves_per_request, _stream(stream)),
-        "APE_LZ4_decompress_range_indexed_batch_dev")
+    _call("APE_LZ4_decompress_range_indexed_batch_dev", _ptr(src_ptrs), _ptr(comp_sizes),
+          _ptr(index), stride, max_segments, nb, _ptr(block_of), _ptr(range_starts),
+          _ptr(range_lens), _ptr(dst_ptrs), _ptr(caps), _ptr(window), _ptr(results), nreq,
+          waves_per_request, _stream(stream))
 
 
 def cdict_size():
@@ -572,38 +564,60 @@ def cdict_window(dict_size, max_src_size):
     return lib().APE_LZ4_cdict_window(dict_size, max_src_size)
 
 
+def _prepare(symbol, what, dict_tensor, max_src_size, cdict_tensor, stream):
+    """cdict_prepare and hc_cdict_prepare: the same arguments, another object."""
+    _bytes(dict_tensor, what + " dict")
+    _bytes(cdict_tensor, what + " cdict")
+    _call(symbol, _ptr(dict_tensor) if dict_tensor.numel() else None, dict_tensor.numel(),
+          max_src_size, _ptr(cdict_tensor), cdict_tensor.numel(), _stream(stream))
+    return cdict_tensor
+
+
 def cdict_prepare(dict_tensor, max_src_size, cdict_tensor, stream=None):
     """APE_LZ4_cdict_prepare_dev: dict_tensor (uint8 CUDA, any placement; may be empty) ->
     the prepared dictionary in cdict_tensor (uint8 CUDA, >= cdict_size() bytes, 16-byte
     aligned) for messages of up to max_src_size bytes.  Returns cdict_tensor."""
-    import torch
-    _arr(dict_tensor, "cdict_prepare dict", torch.uint8)
-    _arr(cdict_tensor, "cdict_prepare cdict", torch.uint8)
-    _check(lib().APE_LZ4_cdict_prepare_dev(
-        _ptr(dict_tensor) if dict_tensor.numel() else None, dict_tensor.numel(), max_src_size,
-        _ptr(cdict_tensor), cdict_tensor.numel(), _stream(stream)), "APE_LZ4_cdict_prepare_dev")
-    return cdict_tensor
+    return _prepare("APE_LZ4_cdict_prepare_dev", "cdict_prepare", dict_tensor, max_src_size,
+                    cdict_tensor, stream)
+
+
+def _cdict_batch(symbol, what, size_fn, src_ptrs, src_sizes, dst_ptrs, caps, results, cdict,
+                 stream, *hc):
+    """Every compressor against a prepared dictionary of at least size_fn() bytes; hc: the
+    high-ratio ones' (max_src_size, depth, scratch)."""
+    n = _ptr_batch(what, _FIVE, src_ptrs, src_sizes, dst_ptrs, caps, results)
+    _bytes(cdict, what + " cdict")
+    if cdict.numel() < size_fn():
+        raise ValueError("%s cdict: smaller than %s()" % (what, size_fn.__name__))
+    if hc:
+        max_src_size, depth, scratch = hc
+        _bytes(scratch, what + " scratch")
+        hc = (max_src_size, depth, _ptr(scratch), scratch.numel())
+    _call(symbol, _ptr(src_ptrs), _ptr(src_sizes), _ptr(dst_ptrs), _ptr(caps), _ptr(results), n,
+          _ptr(cdict), *hc, _stream(stream))
 
 
 def compress_cdict_batch(src_ptrs, src_sizes, dst_ptrs, caps, results, cdict, stream=None):
     """N x (loadDict ; compress_fast_continue) against one prepared dictionary (cdict_prepare);
     pointer-array form (int64 tensors of pointers)."""
-    import torch
-    _arr(src_sizes, "compress_cdict_batch src_sizes", torch.int32)
-    n = src_sizes.shape[0]
-    _ptr_args("compress_cdict_batch", n, src_ptrs=(src_ptrs, _i64()), src_sizes=(src_sizes, _i32()),
-              dst_ptrs=(dst_ptrs, _i64()), caps=(caps, _i32()), results=(results, _i32()))
-    _arr(cdict, "compress_cdict_batch cdict", torch.uint8)
-    if cdict.numel() < cdict_size():
-        raise ValueError("compress_cdict_batch cdict: smaller than cdict_size()")
-    _check(lib().APE_LZ4_compress_usingCDict_batch_dev(
-        _ptr(src_ptrs), _ptr(src_sizes), _ptr(dst_ptrs), _ptr(caps), _ptr(results), n,
-        _ptr(cdict), _stream(stream)), "APE_LZ4_compress_usingCDict_batch_dev")
+    _cdict_batch("APE_LZ4_compress_usingCDict_batch_dev", "compress_cdict_batch", cdict_size,
+                 src_ptrs, src_sizes, dst_ptrs, caps, results, cdict, stream)
 
 
 def compress_hc_scratch_size(nblocks):
     """APE_LZ4_compress_hc_scratch_size: scratch bytes for one pass over nblocks."""
     return lib().APE_LZ4_compress_hc_scratch_size(nblocks)
+
+
+def _hc_batch(symbol, what, src_ptrs, src_sizes, dst_ptrs, caps, results, depth, scratch, stream,
+              *prefix):
+    """The four high-ratio calls on plain blocks; prefix: the withPrefix ones' (prefix_sizes,)."""
+    more = dict(prefix_sizes=prefix[0]) if prefix else {}
+    n = _ptr_batch(what, _FIVE, src_ptrs, src_sizes, dst_ptrs, caps, results, ("prefix_sizes",),
+                   **more)
+    _bytes(scratch, what + " scratch")
+    _call(symbol, _ptr(src_ptrs), _ptr(src_sizes), *map(_ptr, prefix), _ptr(dst_ptrs), _ptr(caps),
+          _ptr(results), n, depth, _ptr(scratch), scratch.numel(), _stream(stream))
 
 
 def compress_hc_ptr_batch(src_ptrs, src_sizes, dst_ptrs, caps, results, depth, scratch,
@@ -612,15 +626,8 @@ def compress_hc_ptr_batch(src_ptrs, src_sizes, dst_ptrs, caps, results, depth, s
     candidates per position (1..256, 0 = the default 64); scratch is a uint8 CUDA tensor of at
     least compress_hc_scratch_size(1) bytes (fewer than compress_hc_scratch_size(N): several
     passes, same bytes).  Allocates nothing, so it can be graph-captured."""
-    import torch
-    _arr(src_sizes, "compress_hc_ptr_batch src_sizes", torch.int32)
-    n = src_sizes.shape[0]
-    _ptr_args("compress_hc_ptr_batch", n, src_ptrs=(src_ptrs, _i64()), src_sizes=(src_sizes, _i32()),
-              dst_ptrs=(dst_ptrs, _i64()), caps=(caps, _i32()), results=(results, _i32()))
-    _arr(scratch, "compress_hc_ptr_batch scratch", torch.uint8)
-    _check(lib().APE_LZ4_compress_hc_batch_dev(
-        _ptr(src_ptrs), _ptr(src_sizes), _ptr(dst_ptrs), _ptr(caps), _ptr(results), n, depth,
-        _ptr(scratch), scratch.numel(), _stream(stream)), "APE_LZ4_compress_hc_batch_dev")
+    _hc_batch("APE_LZ4_compress_hc_batch_dev", "compress_hc_ptr_batch", src_ptrs, src_sizes,
+              dst_ptrs, caps, results, depth, scratch, stream)
 
 
 def compress_hc_prefix_ptr_batch(src_ptrs, src_sizes, prefix_sizes, dst_ptrs, caps, results, depth,
@@ -628,18 +635,8 @@ def compress_hc_prefix_ptr_batch(src_ptrs, src_sizes, prefix_sizes, dst_ptrs, ca
     """compress_hc_ptr_batch with history: the prefix_sizes[i] bytes just before src_ptrs[i]
     (int32 CUDA tensor, or None for no history), of which the last min(prefix, 65536 - size)
     are used; each block decodes with decompress_dict_batch given that history."""
-    import torch
-    what = "compress_hc_prefix_ptr_batch"
-    _arr(src_sizes, what + " src_sizes", torch.int32)
-    n = src_sizes.shape[0]
-    _ptr_args(what, n, src_ptrs=(src_ptrs, _i64()), src_sizes=(src_sizes, _i32()),
-              prefix_sizes=(prefix_sizes, (_i32(), True)), dst_ptrs=(dst_ptrs, _i64()),
-              caps=(caps, _i32()), results=(results, _i32()))
-    _arr(scratch, what + " scratch", torch.uint8)
-    _check(lib().APE_LZ4_compress_hc_withPrefix_batch_dev(
-        _ptr(src_ptrs), _ptr(src_sizes), _ptr(prefix_sizes), _ptr(dst_ptrs), _ptr(caps),
-        _ptr(results), n, depth, _ptr(scratch), scratch.numel(), _stream(stream)),
-        "APE_LZ4_compress_hc_withPrefix_batch_dev")
+    _hc_batch("APE_LZ4_compress_hc_withPrefix_batch_dev", "compress_hc_prefix_ptr_batch",
+              src_ptrs, src_sizes, dst_ptrs, caps, results, depth, scratch, stream, prefix_sizes)
 
 
 def compress_hc_opt_scratch_size(nblocks):
@@ -653,34 +650,16 @@ def compress_hc_opt_ptr_batch(src_ptrs, src_sizes, dst_ptrs, caps, results, dept
     equal blocks, other bytes); scratch is a uint8 CUDA tensor of at least
     compress_hc_opt_scratch_size(1) bytes (fewer than compress_hc_opt_scratch_size(N): several
     passes, same bytes).  Allocates nothing, so it can be graph-captured."""
-    import torch
-    what = "compress_hc_opt_ptr_batch"
-    _arr(src_sizes, what + " src_sizes", torch.int32)
-    n = src_sizes.shape[0]
-    _ptr_args(what, n, src_ptrs=(src_ptrs, _i64()), src_sizes=(src_sizes, _i32()),
-              dst_ptrs=(dst_ptrs, _i64()), caps=(caps, _i32()), results=(results, _i32()))
-    _arr(scratch, what + " scratch", torch.uint8)
-    _check(lib().APE_LZ4_compress_hc_opt_batch_dev(
-        _ptr(src_ptrs), _ptr(src_sizes), _ptr(dst_ptrs), _ptr(caps), _ptr(results), n, depth,
-        _ptr(scratch), scratch.numel(), _stream(stream)), "APE_LZ4_compress_hc_opt_batch_dev")
+    _hc_batch("APE_LZ4_compress_hc_opt_batch_dev", "compress_hc_opt_ptr_batch", src_ptrs,
+              src_sizes, dst_ptrs, caps, results, depth, scratch, stream)
 
 
 def compress_hc_opt_prefix_ptr_batch(src_ptrs, src_sizes, prefix_sizes, dst_ptrs, caps, results,
                                      depth, scratch, stream=None):
     """compress_hc_prefix_ptr_batch with the cost-minimising parse: history, results and
     decoding are the same; the scratch is compress_hc_opt_ptr_batch's."""
-    import torch
-    what = "compress_hc_opt_prefix_ptr_batch"
-    _arr(src_sizes, what + " src_sizes", torch.int32)
-    n = src_sizes.shape[0]
-    _ptr_args(what, n, src_ptrs=(src_ptrs, _i64()), src_sizes=(src_sizes, _i32()),
-              prefix_sizes=(prefix_sizes, (_i32(), True)), dst_ptrs=(dst_ptrs, _i64()),
-              caps=(caps, _i32()), results=(results, _i32()))
-    _arr(scratch, what + " scratch", torch.uint8)
-    _check(lib().APE_LZ4_compress_hc_opt_withPrefix_batch_dev(
-        _ptr(src_ptrs), _ptr(src_sizes), _ptr(prefix_sizes), _ptr(dst_ptrs), _ptr(caps),
-        _ptr(results), n, depth, _ptr(scratch), scratch.numel(), _stream(stream)),
-        "APE_LZ4_compress_hc_opt_withPrefix_batch_dev")
+    _hc_batch("APE_LZ4_compress_hc_opt_withPrefix_batch_dev", "compress_hc_opt_prefix_ptr_batch",
+              src_ptrs, src_sizes, dst_ptrs, caps, results, depth, scratch, stream, prefix_sizes)
 
 
 def compress_large_hc_opt_scratch_size(nblocks, max_src_size, pass_slices=0):
@@ -690,34 +669,28 @@ def compress_large_hc_opt_scratch_size(nblocks, max_src_size, pass_slices=0):
     return lib().APE_LZ4_compress_large_hc_opt_scratch_size(nblocks, max_src_size, pass_slices)
 
 
+def _large_hc_batch(symbol, what, size_fn, src_ptrs, src_sizes, dst_ptrs, caps, results,
+                    max_src_size, depth, restart_bytes, index, scratch, stream):
+    """compress_large_hc_ptr_batch and its cost-minimising twin; size_fn: the scratch size."""
+    n = _ptr_batch(what, _FIVE, src_ptrs, src_sizes, dst_ptrs, caps, results)
+    stride = _index_arg(what, index, n, optional=True)
+    scratch = _large_scratch(what, scratch, src_sizes, size_fn, n, max_src_size)
+    _call(symbol, _ptr(src_ptrs), _ptr(src_sizes), _ptr(dst_ptrs), _ptr(caps), _ptr(results), n,
+          max_src_size, depth, _ptr(scratch), scratch.numel(), restart_bytes, _ptr(index), stride,
+          _stream(stream))
+    return scratch
+
+
 def compress_large_hc_opt_ptr_batch(src_ptrs, src_sizes, dst_ptrs, caps, results, max_src_size,
                                     depth, restart_bytes=0, index=None, scratch=None, stream=None):
     """compress_large_hc_ptr_batch with the cost-minimising parse on the slices: restart points,
     the index and every decoder as there.  scratch: uint8 CUDA tensor of at least
     compress_large_hc_opt_scratch_size(N, max_src_size, 1) bytes, 16-byte aligned; None
     allocates one for a single pass.  Returns the scratch."""
-    import torch
-    what = "compress_large_hc_opt_ptr_batch"
-    _arr(src_sizes, what + " src_sizes", torch.int32)
-    n = src_sizes.shape[0]
-    _ptr_args(what, n, src_ptrs=(src_ptrs, _i64()), src_sizes=(src_sizes, _i32()),
-              dst_ptrs=(dst_ptrs, _i64()), caps=(caps, _i32()), results=(results, _i32()))
-    stride = 0
-    if index is not None:
-        stride = _index_arg(what, index, n)
-    if scratch is None:
-        need = compress_large_hc_opt_scratch_size(n, max_src_size)
-        if need == 0 or need >= 1 << 63:
-            raise ValueError("%s: max_src_size outside [1, 0x7E000000] or too many slices for "
-                             "one call" % what)
-        scratch = torch.empty(need, dtype=torch.uint8, device=src_sizes.device)
-    else:
-        _arr(scratch, what + " scratch", torch.uint8)
-    _check(lib().APE_LZ4_compress_large_hc_opt_batch_dev(
-        _ptr(src_ptrs), _ptr(src_sizes), _ptr(dst_ptrs), _ptr(caps), _ptr(results), n,
-        max_src_size, depth, _ptr(scratch), scratch.numel(), restart_bytes, _ptr(index), stride,
-        _stream(stream)), "APE_LZ4_compress_large_hc_opt_batch_dev")
-    return scratch
+    return _large_hc_batch("APE_LZ4_compress_large_hc_opt_batch_dev",
+                           "compress_large_hc_opt_ptr_batch", compress_large_hc_opt_scratch_size,
+                           src_ptrs, src_sizes, dst_ptrs, caps, results, max_src_size, depth,
+                           restart_bytes, index, scratch, stream)
 
 
 def hc_cdict_size():
@@ -734,14 +707,8 @@ def hc_cdict_prepare(dict_tensor, max_src_size, cdict_tensor, stream=None):
     """APE_LZ4_hc_cdict_prepare_dev: dict_tensor (uint8 CUDA, any placement; may be empty) ->
     the prepared high-ratio dictionary in cdict_tensor (uint8 CUDA, >= hc_cdict_size() bytes,
     16-byte aligned) for messages of up to max_src_size bytes.  Returns cdict_tensor."""
-    import torch
-    _arr(dict_tensor, "hc_cdict_prepare dict", torch.uint8)
-    _arr(cdict_tensor, "hc_cdict_prepare cdict", torch.uint8)
-    _check(lib().APE_LZ4_hc_cdict_prepare_dev(
-        _ptr(dict_tensor) if dict_tensor.numel() else None, dict_tensor.numel(), max_src_size,
-        _ptr(cdict_tensor), cdict_tensor.numel(), _stream(stream)),
-        "APE_LZ4_hc_cdict_prepare_dev")
-    return cdict_tensor
+    return _prepare("APE_LZ4_hc_cdict_prepare_dev", "hc_cdict_prepare", dict_tensor, max_src_size,
+                    cdict_tensor, stream)
 
 
 def compress_hc_cdict_scratch_size(nblocks, max_src_size):
@@ -757,20 +724,9 @@ def compress_hc_cdict_batch(src_ptrs, src_sizes, dst_ptrs, caps, results, cdict,
     compress_hc_cdict_scratch_size(1, max_src_size) bytes (fewer than ..._scratch_size(N, ...):
     several passes, same bytes).  Each block decodes with decompress_dict_batch given the
     original dictionary.  Allocates nothing, so it can be graph-captured."""
-    import torch
-    what = "compress_hc_cdict_batch"
-    _arr(src_sizes, what + " src_sizes", torch.int32)
-    n = src_sizes.shape[0]
-    _ptr_args(what, n, src_ptrs=(src_ptrs, _i64()), src_sizes=(src_sizes, _i32()),
-              dst_ptrs=(dst_ptrs, _i64()), caps=(caps, _i32()), results=(results, _i32()))
-    _arr(cdict, what + " cdict", torch.uint8)
-    if cdict.numel() < hc_cdict_size():
-        raise ValueError(what + " cdict: smaller than hc_cdict_size()")
-    _arr(scratch, what + " scratch", torch.uint8)
-    _check(lib().APE_LZ4_compress_hc_usingCDict_batch_dev(
-        _ptr(src_ptrs), _ptr(src_sizes), _ptr(dst_ptrs), _ptr(caps), _ptr(results), n,
-        _ptr(cdict), max_src_size, depth, _ptr(scratch), scratch.numel(), _stream(stream)),
-        "APE_LZ4_compress_hc_usingCDict_batch_dev")
+    _cdict_batch("APE_LZ4_compress_hc_usingCDict_batch_dev", "compress_hc_cdict_batch",
+                 hc_cdict_size, src_ptrs, src_sizes, dst_ptrs, caps, results, cdict, stream,
+                 max_src_size, depth, scratch)
 
 
 def compress_hc_opt_cdict_scratch_size(nblocks, max_src_size):
@@ -785,20 +741,9 @@ def compress_hc_opt_cdict_batch(src_ptrs, src_sizes, dst_ptrs, caps, results, cd
     compress_hc_opt_cdict_scratch_size(1, max_src_size) bytes (fewer than ..._scratch_size(N,
     ...): several passes, same bytes).  A block that does not fit its capacity gets result 0
     and nothing is written to it.  Allocates nothing, so it can be graph-captured."""
-    import torch
-    what = "compress_hc_opt_cdict_batch"
-    _arr(src_sizes, what + " src_sizes", torch.int32)
-    n = src_sizes.shape[0]
-    _ptr_args(what, n, src_ptrs=(src_ptrs, _i64()), src_sizes=(src_sizes, _i32()),
-              dst_ptrs=(dst_ptrs, _i64()), caps=(caps, _i32()), results=(results, _i32()))
-    _arr(cdict, what + " cdict", torch.uint8)
-    if cdict.numel() < hc_cdict_size():
-        raise ValueError(what + " cdict: smaller than hc_cdict_size()")
-    _arr(scratch, what + " scratch", torch.uint8)
-    _check(lib().APE_LZ4_compress_hc_opt_usingCDict_batch_dev(
-        _ptr(src_ptrs), _ptr(src_sizes), _ptr(dst_ptrs), _ptr(caps), _ptr(results), n,
-        _ptr(cdict), max_src_size, depth, _ptr(scratch), scratch.numel(), _stream(stream)),
-        "APE_LZ4_compress_hc_opt_usingCDict_batch_dev")
+    _cdict_batch("APE_LZ4_compress_hc_opt_usingCDict_batch_dev", "compress_hc_opt_cdict_batch",
+                 hc_cdict_size, src_ptrs, src_sizes, dst_ptrs, caps, results, cdict, stream,
+                 max_src_size, depth, scratch)
 
 
 def compress_large_hc_scratch_size(nblocks, max_src_size, pass_slices=0):
@@ -815,41 +760,19 @@ def compress_large_hc_ptr_batch(src_ptrs, src_sizes, dst_ptrs, caps, results, ma
     scratch: uint8 CUDA tensor of at least compress_large_hc_scratch_size(N, max_src_size, 1)
     bytes, 16-byte aligned (fewer than ..._scratch_size(N, max_src_size): several passes, same
     bytes); None allocates one for a single pass.  Returns the scratch."""
-    import torch
-    what = "compress_large_hc_ptr_batch"
-    _arr(src_sizes, what + " src_sizes", torch.int32)
-    n = src_sizes.shape[0]
-    _ptr_args(what, n, src_ptrs=(src_ptrs, _i64()), src_sizes=(src_sizes, _i32()),
-              dst_ptrs=(dst_ptrs, _i64()), caps=(caps, _i32()), results=(results, _i32()))
-    stride = 0
-    if index is not None:
-        stride = _index_arg(what, index, n)
-    if scratch is None:
-        need = compress_large_hc_scratch_size(n, max_src_size)
-        if need == 0 or need >= 1 << 63:
-            raise ValueError("%s: max_src_size outside [1, 0x7E000000] or too many slices for "
-                             "one call" % what)
-        scratch = torch.empty(need, dtype=torch.uint8, device=src_sizes.device)
-    else:
-        _arr(scratch, what + " scratch", torch.uint8)
-    _check(lib().APE_LZ4_compress_large_hc_batch_dev(
-        _ptr(src_ptrs), _ptr(src_sizes), _ptr(dst_ptrs), _ptr(caps), _ptr(results), n,
-        max_src_size, depth, _ptr(scratch), scratch.numel(), restart_bytes, _ptr(index), stride,
-        _stream(stream)), "APE_LZ4_compress_large_hc_batch_dev")
-    return scratch
+    return _large_hc_batch("APE_LZ4_compress_large_hc_batch_dev", "compress_large_hc_ptr_batch",
+                           compress_large_hc_scratch_size, src_ptrs, src_sizes, dst_ptrs, caps,
+                           results, max_src_size, depth, restart_bytes, index, scratch, stream)
 
 
 def decompress_dict_batch(src_ptrs, comp_sizes, dst_ptrs, caps, dict_ptrs, dict_sizes, results,
                           stream=None):
     """N x APE_LZ4_decompress_safe_usingDict, pointer-array form (int64 tensors)."""
-    n = comp_sizes.shape[0]
-    _ptr_args("decompress_dict_batch", n, src_ptrs=(src_ptrs, _i64()), comp_sizes=(comp_sizes, _i32()),
-              dst_ptrs=(dst_ptrs, _i64()), caps=(caps, _i32()), dict_ptrs=(dict_ptrs, _i64()),
-              dict_sizes=(dict_sizes, _i32()), results=(results, _i32()))
-    _check(lib().APE_LZ4_decompress_safe_usingDict_batch_dev(
-        _ptr(src_ptrs), _ptr(comp_sizes), _ptr(dst_ptrs), _ptr(caps), _ptr(dict_ptrs),
-        _ptr(dict_sizes), _ptr(results), n, _stream(stream)),
-        "APE_LZ4_decompress_safe_usingDict_batch_dev")
+    n = _ptr_batch("decompress_dict_batch", _DECODE, src_ptrs, comp_sizes, dst_ptrs, caps,
+                   results, dict_ptrs=dict_ptrs, dict_sizes=dict_sizes)
+    _call("APE_LZ4_decompress_safe_usingDict_batch_dev", _ptr(src_ptrs), _ptr(comp_sizes),
+          _ptr(dst_ptrs), _ptr(caps), _ptr(dict_ptrs), _ptr(dict_sizes), _ptr(results), n,
+          _stream(stream))
 
 
 def synth_blocks(dst, block_size, first_block, kind, stream=None):

@@ -4,7 +4,13 @@
 //
 // No CPU fallback anywhere: without a usable gfx950 device every entry point
 // returns APE_LZ4_GPU_ENODEV (and the one-shot API reports failure).
+//
+// Every launcher reads: fill the kernel's argument struct, check the arguments, check the
+// device, launch.  The argument checks come before the device check, so a bad call fails the
+// same way on any machine (the few places that keep another order say so).
+#include <initializer_list>
 #include <mutex>
+#include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
 #include <vector>
@@ -22,6 +28,32 @@ thread_local char g_err[256] = "";
 void set_err(const char *what, hipError_t e) {
     snprintf(g_err, sizeof g_err, "%s: %s", what, e == hipSuccess ? "ok" : hipGetErrorString(e));
 }
+
+// The one way to reject a call.  Every message starts with the entry point's name (its symbol
+// without the APE_LZ4_ prefix), so APE_LZ4_gpu_last_error() never shows an earlier call's text.
+__attribute__((format(printf, 1, 2))) int einval(const char *fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_err, sizeof g_err, fmt, ap);
+    va_end(ap);
+    return APE_LZ4_GPU_EINVAL;
+}
+
+// a negative count, or a null array in a batch that has entries
+bool bad_arrays(int n, std::initializer_list<const void *> arrays) {
+    bool bad = n < 0;
+    if (n > 0)
+        for (const void *p : arrays) bad |= !p;
+    return bad;
+}
+
+int check_arrays(const char *who, int n, std::initializer_list<const void *> arrays) {
+    if (!bad_arrays(n, arrays)) return APE_LZ4_GPU_OK;
+    return einval("%s: invalid argument (a null array or a negative count, nblocks %d)", who, n);
+}
+
+inline bool aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
+inline size_t up16(size_t x) { return (x + 15) & ~(size_t)15; }
 
 int g_ndev = -1;
 std::vector<int> g_dev_ok;  // per device: 1 = gfx950
@@ -60,6 +92,22 @@ int finish_launch(hipError_t e, const char *what) {
     }
     return APE_LZ4_GPU_OK;
 }
+
+// The events of a timed call: all created or the call fails, all destroyed on every way out.
+struct Events {
+    std::vector<hipEvent_t> ev;
+    explicit Events(int n) : ev((size_t)n, nullptr) {}
+    Events(const Events &) = delete;
+    ~Events() {
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+    int create() {
+        hipError_t e = hipSuccess;
+        for (size_t q = 0; q < ev.size() && e == hipSuccess; q++) e = hipEventCreate(&ev[q]);
+        return finish_launch(e, "hipEventCreate");
+    }
+};
 
 // ---- pinned staging for the host-buffer path: a process-wide pool ----
 // A call borrows one context (stream + pinned + device staging) for its duration and
@@ -139,64 +187,9 @@ int host_reserve(HostCtx &c, size_t bytes) {
     return APE_LZ4_GPU_OK;
 }
 
-inline size_t up16(size_t x) { return (x + 15) & ~(size_t)15; }
-
 // Staging layout (same offsets on host and device):
 //   [ptr arrays: src, dst][int arrays: in_size, cap, target, result][inputs][outputs]
 // mode: 0 = compress, 1 = decompress_safe, 2 = decompress_safe_partial
-int host_batch_run(HostCtx &ctx, int mode, int accel, const char *const *h_src, const int *h_in,
-                   char *const *h_dst, const int *h_cap, const int *h_target, int *h_res, int nb,
-                   const std::vector<size_t> &in_off, const std::vector<size_t> &out_off,
-                   const std::vector<size_t> &out_len, size_t total);
-
-int host_batch(int mode, int accel, const char *const *h_src, const int *h_in, char *const *h_dst,
-               const int *h_cap, const int *h_target, int *h_res, int nb) {
-    if (nb < 0 || (nb > 0 && (!h_src || !h_in || !h_dst || !h_cap || !h_res))) {
-        snprintf(g_err, sizeof g_err, "invalid argument");
-        return APE_LZ4_GPU_EINVAL;
-    }
-    int rc = check_device();
-    if (rc) return rc;
-    if (nb == 0) return APE_LZ4_GPU_OK;
-    std::vector<size_t> in_off(nb), out_off(nb), out_len(nb);
-    size_t meta = up16((size_t)nb * 2 * sizeof(void *)) + up16((size_t)nb * 4 * sizeof(int));
-    size_t pos = meta;
-    for (int i = 0; i < nb; i++) {
-        in_off[i] = pos;
-        size_t len = h_in[i] > 0 ? (size_t)h_in[i] : 1;  // size <= 0 still reads src[0]
-        pos += up16(len);
-    }
-    for (int i = 0; i < nb; i++) {
-        out_off[i] = pos;
-        size_t lim;
-        if (mode == 0) {
-            int n = h_in[i] > 0 ? h_in[i] : 0;
-            size_t bound = (size_t)n + n / 255 + 16;
-            lim = h_cap[i] <= 0 ? 0 : ((size_t)h_cap[i] < bound ? (size_t)h_cap[i] : bound);
-        } else {
-            // the decoder writes only decoded bytes, and LZ4 expands at most 255x (a
-            // 255 length byte per 255 output bytes): a huge cap needs no huge staging
-            const size_t cs = h_in[i] > 0 ? (size_t)h_in[i] : 0;
-            const size_t most = 255 * cs + 64;
-            lim = h_cap[i] <= 0 ? 0 : ((size_t)h_cap[i] < most ? (size_t)h_cap[i] : most);
-        }
-        out_len[i] = lim;
-        pos += up16(lim ? lim : 1);
-    }
-    const size_t total = pos;
-    HostCtx *ctx = ctx_acquire();
-    if (!ctx) return APE_LZ4_GPU_ENOMEM;
-    rc = host_reserve(*ctx, total);
-    if (rc) { ctx_return(ctx); return rc; }
-    rc = host_batch_run(*ctx, mode, accel, h_src, h_in, h_dst, h_cap, h_target, h_res, nb,
-                        in_off, out_off, out_len, total);
-    // a failed run may have left copies or the kernel queued on the context's stream:
-    // drain them before another caller can borrow its pinned buffer
-    if (rc) (void)hipStreamSynchronize(ctx->stream);
-    ctx_return(ctx);
-    return rc;
-}
-
 int host_batch_run(HostCtx &ctx, int mode, int accel, const char *const *h_src, const int *h_in,
                    char *const *h_dst, const int *h_cap, const int *h_target, int *h_res, int nb,
                    const std::vector<size_t> &in_off, const std::vector<size_t> &out_off,
@@ -245,6 +238,53 @@ int host_batch_run(HostCtx &ctx, int mode, int accel, const char *const *h_src, 
     return APE_LZ4_GPU_OK;
 }
 
+int host_batch(const char *who, int mode, int accel, const char *const *h_src, const int *h_in,
+               char *const *h_dst, const int *h_cap, const int *h_target, int *h_res, int nb) {
+    if (int rc = check_arrays(who, nb, {h_src, h_in, h_dst, h_cap, h_res})) return rc;
+    int rc = check_device();
+    if (rc) return rc;
+    if (nb == 0) return APE_LZ4_GPU_OK;
+    std::vector<size_t> in_off(nb), out_off(nb), out_len(nb);
+    size_t meta = up16((size_t)nb * 2 * sizeof(void *)) + up16((size_t)nb * 4 * sizeof(int));
+    size_t pos = meta;
+    for (int i = 0; i < nb; i++) {
+        in_off[i] = pos;
+        size_t len = h_in[i] > 0 ? (size_t)h_in[i] : 1;  // size <= 0 still reads src[0]
+        pos += up16(len);
+    }
+    for (int i = 0; i < nb; i++) {
+        out_off[i] = pos;
+        size_t lim;
+        if (mode == 0) {
+            int n = h_in[i] > 0 ? h_in[i] : 0;
+            size_t bound = (size_t)n + n / 255 + 16;
+            lim = h_cap[i] <= 0 ? 0 : ((size_t)h_cap[i] < bound ? (size_t)h_cap[i] : bound);
+        } else {
+            // the decoder writes only decoded bytes, and LZ4 expands at most 255x (a
+            // 255 length byte per 255 output bytes): a huge cap needs no huge staging
+            const size_t cs = h_in[i] > 0 ? (size_t)h_in[i] : 0;
+            const size_t most = 255 * cs + 64;
+            lim = h_cap[i] <= 0 ? 0 : ((size_t)h_cap[i] < most ? (size_t)h_cap[i] : most);
+        }
+        out_len[i] = lim;
+        pos += up16(lim ? lim : 1);
+    }
+    const size_t total = pos;
+    HostCtx *ctx = ctx_acquire();
+    if (!ctx) return APE_LZ4_GPU_ENOMEM;
+    rc = host_reserve(*ctx, total);
+    if (rc) { ctx_return(ctx); return rc; }
+    rc = host_batch_run(*ctx, mode, accel, h_src, h_in, h_dst, h_cap, h_target, h_res, nb,
+                        in_off, out_off, out_len, total);
+    // a failed run may have left copies or the kernel queued on the context's stream:
+    // drain them before another caller can borrow its pinned buffer
+    if (rc) (void)hipStreamSynchronize(ctx->stream);
+    ctx_return(ctx);
+    return rc;
+}
+
+// ---- the kernels' argument structs from the caller's arguments, and the checks on them ----
+// the pointer-array form: block i at src[i], written to dst[i]
 BlockArgs ptr_args(const char *const *src, const int *in, char *const *dst, const int *cap,
                    const int *tgt, int *res, int nb) {
     BlockArgs a{};
@@ -258,177 +298,61 @@ BlockArgs ptr_args(const char *const *src, const int *in, char *const *dst, cons
     return a;
 }
 
-}  // namespace
-
-extern "C" {
-
-int APE_LZ4_gpu_init(void) { return check_device(); }
-
-int APE_LZ4_gpu_device_count(void) {
-    std::call_once(g_once, probe);
-    return g_ndev < 0 ? 0 : g_ndev;
+// arguments, then device; `more`: the arrays an entry point takes beyond the standard five
+int ready_ptr(const char *who, const BlockArgs &a, std::initializer_list<const void *> more = {}) {
+    if (int rc = check_arrays(who, a.nblocks, {a.src, a.src_size, a.dst, a.dst_cap, a.result}))
+        return rc;
+    if (int rc = check_arrays(who, a.nblocks, more)) return rc;
+    return check_device();
 }
 
-const char *APE_LZ4_gpu_last_error(void) { return g_err; }
-const char *APE_LZ4_gpu_arch(void) { return "gfx950"; }
-
-int APE_LZ4_compress_batch_dev(const char *const *d_src, const int *d_srcSize,
-                               char *const *d_dst, const int *d_dstCap, int *d_result,
-                               int nblocks, void *stream) {
-    if (nblocks < 0 || (nblocks > 0 && (!d_src || !d_srcSize || !d_dst || !d_dstCap || !d_result)))
-        return APE_LZ4_GPU_EINVAL;
-    int rc = check_device();
-    if (rc) return rc;
-    return finish_launch(launch_encode(ptr_args(d_src, d_srcSize, d_dst, d_dstCap, nullptr,
-                                                d_result, nblocks),
-                                       (hipStream_t)stream),
-                         "lz4_encode_kernel");
+// the strided form: block i at src + i * src_stride, written to dst + i * dst_stride
+BlockArgs strided_args(const char *src, size_t src_stride, const int *in, char *dst,
+                       size_t dst_stride, const int *cap, int *res, int nb) {
+    BlockArgs a{};
+    a.src_base = src;
+    a.dst_base = dst;
+    a.src_stride = src_stride;
+    a.dst_stride = dst_stride;
+    a.src_size = in;
+    a.dst_cap = cap;
+    a.result = res;
+    a.nblocks = nb;
+    return a;
 }
 
-int APE_LZ4_compress_fast_batch_dev(const char *const *d_src, const int *d_srcSize,
-                                    char *const *d_dst, const int *d_dstCap, int *d_result,
-                                    int nblocks, int acceleration, void *stream) {
-    if (nblocks < 0 || (nblocks > 0 && (!d_src || !d_srcSize || !d_dst || !d_dstCap || !d_result)))
-        return APE_LZ4_GPU_EINVAL;
-    int rc = check_device();
-    if (rc) return rc;
-    BlockArgs a = ptr_args(d_src, d_srcSize, d_dst, d_dstCap, nullptr, d_result, nblocks);
-    a.accel = acceleration;
-    return finish_launch(launch_encode(a, (hipStream_t)stream), "lz4_encode_kernel");
+// arguments, then device; the blocks' places come from their sizes or, in a framed stream, from
+// the offsets, and without capacities the capacity is the stride, which then has to fit an int
+int ready_strided(const char *who, const BlockArgs &a) {
+    const void *places = a.frame_off ? (const void *)a.frame_off : a.src_size;
+    if (int rc = check_arrays(who, a.nblocks, {a.src_base, places, a.dst_base, a.result}))
+        return rc;
+    if (!a.dst_cap && a.dst_stride > 0x7FFFFFFF)
+        return einval("%s: dst stride %zu needs explicit capacities", who, a.dst_stride);
+    return check_device();
 }
 
-int APE_LZ4_compress_exact_batch_dev(const char *const *d_src, const int *d_srcSize,
-                                     char *const *d_dst, const int *d_dstCap, int *d_result,
-                                     int nblocks, int acceleration, void *stream) {
-    if (nblocks < 0 || (nblocks > 0 && (!d_src || !d_srcSize || !d_dst || !d_dstCap || !d_result)))
-        return APE_LZ4_GPU_EINVAL;
-    int rc = check_device();
-    if (rc) return rc;
-    BlockArgs a = ptr_args(d_src, d_srcSize, d_dst, d_dstCap, nullptr, d_result, nblocks);
-    a.accel = acceleration;
-    return finish_launch(launch_encode_exact(a, (hipStream_t)stream), "lz4_encode_exact_kernel");
-}
-
-int APE_LZ4_decompress_safe_batch_dev(const char *const *d_src, const int *d_compressedSize,
-                                      char *const *d_dst, const int *d_maxDecompressedSize,
-                                      int *d_result, int nblocks, void *stream) {
-    if (nblocks < 0 || (nblocks > 0 && (!d_src || !d_compressedSize || !d_dst ||
-                                         !d_maxDecompressedSize || !d_result)))
-        return APE_LZ4_GPU_EINVAL;
-    int rc = check_device();
-    if (rc) return rc;
-    return finish_launch(launch_decode(ptr_args(d_src, d_compressedSize, d_dst,
-                                                d_maxDecompressedSize, nullptr, d_result, nblocks),
-                                       false, (hipStream_t)stream),
-                         "lz4_decode_kernel");
-}
-
-int APE_LZ4_decompress_safe_partial_batch_dev(const char *const *d_src,
-                                              const int *d_compressedSize, char *const *d_dst,
-                                              const int *d_targetOutputSize,
-                                              const int *d_maxDecompressedSize, int *d_result,
-                                              int nblocks, void *stream) {
-    if (nblocks < 0 || (nblocks > 0 && (!d_src || !d_compressedSize || !d_dst ||
-                                         !d_targetOutputSize || !d_maxDecompressedSize ||
-                                         !d_result)))
-        return APE_LZ4_GPU_EINVAL;
-    int rc = check_device();
-    if (rc) return rc;
-    return finish_launch(launch_decode(ptr_args(d_src, d_compressedSize, d_dst,
-                                                d_maxDecompressedSize, d_targetOutputSize,
-                                                d_result, nblocks),
-                                       true, (hipStream_t)stream),
-                         "lz4_decode_kernel<partial>");
-}
-
-int APE_LZ4_decompress_safe_usingDict_batch_dev(const char *const *d_src,
-                                                const int *d_compressedSize, char *const *d_dst,
-                                                const int *d_maxDecompressedSize,
-                                                const char *const *d_dict, const int *d_dictSize,
-                                                int *d_result, int nblocks, void *stream) {
-    if (nblocks < 0 || (nblocks > 0 && (!d_src || !d_compressedSize || !d_dst ||
-                                         !d_maxDecompressedSize || !d_dict || !d_dictSize ||
-                                         !d_result)))
-        return APE_LZ4_GPU_EINVAL;
-    int rc = check_device();
-    if (rc) return rc;
-    BlockArgs a = ptr_args(d_src, d_compressedSize, d_dst, d_maxDecompressedSize, nullptr,
-                           d_result, nblocks);
-    a.dict = d_dict;
-    a.dict_size = d_dictSize;
-    return finish_launch(launch_decode(a, false, (hipStream_t)stream),
-                         "lz4_decode_kernel<usingDict>");
-}
-
-int APE_LZ4_decompress_fast_batch_dev(const char *const *d_src, const int *d_srcBound,
-                                      char *const *d_dst, const int *d_originalSize,
-                                      int *d_result, int nblocks, void *stream) {
-    if (nblocks < 0 || (nblocks > 0 && (!d_src || !d_srcBound || !d_dst || !d_originalSize ||
-                                         !d_result)))
-        return APE_LZ4_GPU_EINVAL;
-    int rc = check_device();
-    if (rc) return rc;
-    BlockArgs a = ptr_args(d_src, d_srcBound, d_dst, d_originalSize, nullptr, d_result, nblocks);
-    a.fast = 1;
-    return finish_launch(launch_decode(a, false, (hipStream_t)stream), "lz4_decode_kernel<fast>");
-}
-
-int APE_LZ4_compress_withPrefix_batch_dev(const char *const *d_src, const int *d_srcSize,
-                                          const int *d_prefixSize, char *const *d_dst,
-                                          const int *d_dstCap, int *d_result, int nblocks,
-                                          void *stream) {
-    if (nblocks < 0 || (nblocks > 0 && (!d_src || !d_srcSize || !d_prefixSize || !d_dst ||
-                                         !d_dstCap || !d_result)))
-        return APE_LZ4_GPU_EINVAL;
-    int rc = check_device();
-    if (rc) return rc;
-    BlockArgs a = ptr_args(d_src, d_srcSize, d_dst, d_dstCap, nullptr, d_result, nblocks);
-    a.dict_size = d_prefixSize;
-    return finish_launch(launch_encode(a, (hipStream_t)stream), "lz4_encode_kernel<prefix>");
-}
-
-// ---- prepared dictionaries (lz4_cdict.hip, the encoder's EXT instantiation) ----
-size_t APE_LZ4_cdict_size(void) { return (size_t)kCdSize; }
-
-int APE_LZ4_cdict_window(int dictSize, int maxSrcSize) {
-    if (dictSize < 0 || maxSrcSize < 1 || maxSrcSize > kMaxBlock) return -1;
-    const int D = cdict_window(dictSize, maxSrcSize);
-    return D < 64 ? 0 : D;
-}
-
-int APE_LZ4_cdict_prepare_dev(const char *d_dict, int dictSize, int maxSrcSize, void *d_cdict,
-                              size_t cdict_bytes, void *stream) {
+// both kinds of prepared dictionary: an object of `size` bytes for messages up to maxSrcSize
+int ready_prepare(const char *who, const char *d_dict, int dictSize, int maxSrcSize,
+                  const void *d_cdict, size_t cdict_bytes, uint32_t size) {
     if (dictSize < 0 || (dictSize > 0 && !d_dict) || maxSrcSize < 1 || maxSrcSize > kMaxBlock ||
-        !d_cdict || cdict_bytes < (size_t)kCdSize || ((uintptr_t)d_cdict & 15u)) {
-        snprintf(g_err, sizeof g_err, "cdict_prepare: dictSize %d, maxSrcSize %d (1..%d), object "
-                 "of %zu bytes at %p (need %u bytes, 16-byte aligned)", dictSize, maxSrcSize,
-                 kMaxBlock, cdict_bytes, d_cdict, kCdSize);
-        return APE_LZ4_GPU_EINVAL;
-    }
-    int rc = check_device();
-    if (rc) return rc;
-    return finish_launch(launch_cdict_prepare(d_dict, dictSize, maxSrcSize, d_cdict,
-                                              (hipStream_t)stream),
-                         "lz4_cdict_prepare_kernel");
+        !d_cdict || cdict_bytes < (size_t)size || !aligned16(d_cdict))
+        return einval("%s: dictSize %d, maxSrcSize %d (1..%d), object of %zu bytes at %p (need "
+                      "%u bytes, 16-byte aligned)", who, dictSize, maxSrcSize, kMaxBlock,
+                      cdict_bytes, d_cdict, size);
+    return check_device();
 }
 
-int APE_LZ4_compress_usingCDict_batch_dev(const char *const *d_src, const int *d_srcSize,
-                                          char *const *d_dst, const int *d_dstCap, int *d_result,
-                                          int nblocks, const void *d_cdict, void *stream) {
-    if (nblocks < 0 || !d_cdict || ((uintptr_t)d_cdict & 15u) ||
-        (nblocks > 0 && (!d_src || !d_srcSize || !d_dst || !d_dstCap || !d_result)))
-        return APE_LZ4_GPU_EINVAL;
-    int rc = check_device();
-    if (rc) return rc;
-    return finish_launch(launch_encode_cdict(ptr_args(d_src, d_srcSize, d_dst, d_dstCap, nullptr,
-                                                      d_result, nblocks),
-                                             d_cdict, (hipStream_t)stream),
-                         "lz4_encode_cdict_kernel");
+// blocks per pass: as many as the scratch holds of `slot` bytes each, at most `most` and no
+// more than the batch has
+int pass_blocks(size_t scratch_bytes, size_t slot, int most, int nblocks) {
+    const size_t fit = scratch_bytes / slot;
+    const int sub = fit < (size_t)most ? (int)fit : most;
+    return sub > nblocks ? nblocks : sub;
 }
 
-namespace {
-
-constexpr int kDsSub = 16384;   // destSize: blocks per scratch pass
+// ---- compress_destSize (lz4_destsize.hip) ----
+constexpr int kDsSub = 16384;   // blocks per scratch pass
 inline size_t ds_stride() { return up16((size_t)kMaxBlock + kMaxBlock / 255 + 16); }
 inline size_t ds_scratch(int sub) { return (size_t)sub * ds_stride() + (size_t)sub * sizeof(int); }
 
@@ -457,32 +381,405 @@ hipError_t destsize_passes(const char *const *d_src, int *d_srcSize, char *const
     return e;
 }
 
+// ---- the high-ratio mode (lz4_encode_hc.hip, lz4_hc_cdict.hip) ----
+constexpr int kHcSub = 1024;   // blocks per scratch pass: 262144 search workgroups
+
+// d_prefixSize (nullable): per-block bytes of history before d_src[i]; opt: the cost-minimising
+// parse, whose cost tables follow the match tables in the scratch.  The scratch has to hold one
+// block whatever nblocks is.
+int hc_batch(const char *who, bool opt, const char *const *d_src, const int *d_srcSize,
+             const int *d_prefixSize, char *const *d_dst, const int *d_dstCap, int *d_result,
+             int nblocks, int depth, void *d_scratch, size_t scratch_bytes, void *stream) {
+    const size_t slot = opt ? kHcOptSlotBytes : kHcSlotBytes;
+    if (depth < 0 || depth > kHcMaxDepth || !d_scratch || !aligned16(d_scratch) ||
+        scratch_bytes < slot || bad_arrays(nblocks, {d_src, d_srcSize, d_dst, d_dstCap, d_result}))
+        return einval("%s: nblocks %d, depth %d (0..%d), scratch of %zu bytes at %p (need %zu "
+                      "bytes, 16-byte aligned)", who, nblocks, depth, kHcMaxDepth, scratch_bytes,
+                      d_scratch, slot);
+    if (int rc = check_device()) return rc;
+    const int sub = pass_blocks(scratch_bytes, slot, kHcSub, nblocks);
+    hipError_t e = hipSuccess;
+    for (int off = 0; off < nblocks && e == hipSuccess; off += sub) {
+        HcOptArgs o{};
+        HcArgs &a = o.a;
+        a.src = d_src + off;
+        a.src_size = d_srcSize + off;
+        a.dst = d_dst + off;
+        a.dst_cap = d_dstCap + off;
+        a.result = d_result + off;
+        a.prefix = d_prefixSize ? d_prefixSize + off : nullptr;
+        a.nblocks = nblocks - off < sub ? nblocks - off : sub;
+        a.depth = depth ? depth : kHcDefaultDepth;
+        a.chain = (uint16_t *)d_scratch;
+        a.match = (uint32_t *)((char *)d_scratch + (size_t)sub * kHcChainBytes);
+        o.cost = (uint32_t *)((char *)d_scratch + (size_t)sub * kHcSlotBytes);
+        e = opt ? launch_encode_hc_opt(o, (hipStream_t)stream)
+                : launch_encode_hc(a, (hipStream_t)stream);
+    }
+    return finish_launch(e, opt ? "lz4_hc_chain_kernel + lz4_hc_search_kernel + "
+                                  "lz4_hc_opt_parse_kernel"
+                                : "lz4_hc_chain_kernel + lz4_hc_search_kernel + "
+                                  "lz4_hc_parse_kernel");
+}
+
+// messages per scratch pass against a prepared dictionary: as many as make kHcSub x 256 search
+// workgroups
+inline int hc_cdict_sub(int maxSrcSize) {
+    return kHcSub * (kMaxBlock / kHcdThreads) / hc_cdict_groups(maxSrcSize);
+}
+
+size_t hc_cdict_scratch(int nblocks, int maxSrcSize, bool opt) {
+    if (nblocks <= 0 || maxSrcSize < 1 || maxSrcSize > kMaxBlock) return 0;
+    const int sub = hc_cdict_sub(maxSrcSize);
+    return (size_t)(nblocks < sub ? nblocks : sub) *
+           (opt ? hc_cdict_opt_slot_bytes(maxSrcSize) : hc_cdict_slot_bytes(maxSrcSize));
+}
+
+// opt, and the scratch at nblocks == 0: as hc_batch
+int hc_cdict_batch(const char *who, bool opt, const char *const *d_src, const int *d_srcSize,
+                   char *const *d_dst, const int *d_dstCap, int *d_result, int nblocks,
+                   const void *d_cdict, int maxSrcSize, int depth, void *d_scratch,
+                   size_t scratch_bytes, void *stream) {
+    const bool range = maxSrcSize >= 1 && maxSrcSize <= kMaxBlock;
+    const size_t slot = !range ? 0 : opt ? hc_cdict_opt_slot_bytes(maxSrcSize)
+                                         : hc_cdict_slot_bytes(maxSrcSize);
+    if (!range || depth < 0 || depth > kHcMaxDepth || !d_cdict || !aligned16(d_cdict) ||
+        !d_scratch || !aligned16(d_scratch) || scratch_bytes < slot ||
+        bad_arrays(nblocks, {d_src, d_srcSize, d_dst, d_dstCap, d_result}))
+        return einval("%s: nblocks %d, maxSrcSize %d (1..%d), depth %d (0..%d), object at %p, "
+                      "scratch of %zu bytes at %p (need %zu bytes; both 16-byte aligned)", who,
+                      nblocks, maxSrcSize, kMaxBlock, depth, kHcMaxDepth, d_cdict, scratch_bytes,
+                      d_scratch, slot);
+    if (int rc = check_device()) return rc;
+    const int sub = pass_blocks(scratch_bytes, slot, hc_cdict_sub(maxSrcSize), nblocks);
+    hipError_t e = hipSuccess;
+    for (int off = 0; off < nblocks && e == hipSuccess; off += sub) {
+        HcDictOptArgs o{};
+        HcDictArgs &a = o.a;
+        a.src = d_src + off;
+        a.src_size = d_srcSize + off;
+        a.dst = d_dst + off;
+        a.dst_cap = d_dstCap + off;
+        a.result = d_result + off;
+        a.nblocks = nblocks - off < sub ? nblocks - off : sub;
+        a.depth = depth ? depth : kHcDefaultDepth;
+        a.max_src = maxSrcSize;
+        a.cdict = (const uint8_t *)d_cdict;
+        a.chain_stride = (uint32_t)hc_cdict_chain_entries(maxSrcSize);
+        a.match_stride = (uint32_t)hc_cdict_match_entries(maxSrcSize);
+        a.chain = (uint16_t *)d_scratch;
+        a.match = (uint32_t *)((char *)d_scratch + (size_t)sub * a.chain_stride * sizeof(uint16_t));
+        o.cost_stride = (uint32_t)hc_cdict_cost_entries(maxSrcSize);
+        o.cost = (uint32_t *)((char *)d_scratch + (size_t)sub * hc_cdict_slot_bytes(maxSrcSize));
+        e = opt ? launch_encode_hc_cdict_opt(o, (hipStream_t)stream)
+                : launch_encode_hc_cdict(a, (hipStream_t)stream);
+    }
+    return finish_launch(e, opt ? "lz4_hc_cdict_chain_kernel + lz4_hc_cdict_search_kernel + "
+                                  "lz4_hc_cdict_opt_parse_kernel"
+                                : "lz4_hc_cdict_chain_kernel + lz4_hc_cdict_search_kernel + "
+                                  "lz4_hc_cdict_parse_kernel");
+}
+
+// ---- inputs of any size as one block (lz4_large.hip) ----
+constexpr int kLargeMaxSrc = 0x7E000000;   // LZ4_MAX_INPUT_SIZE (ref src/ape_lz4.h)
+
+bool large_src_ok(int maxSrcSize) { return maxSrcSize >= 1 && maxSrcSize <= kLargeMaxSrc; }
+// restartBytes: 0 or a positive multiple of the slice size
+bool restart_ok(int restartBytes) {
+    return restartBytes >= 0 && restartBytes % large_slice_size() == 0;
+}
+
+// the caller's side of LargeArgs; buf is the whole scratch until large_layout cuts it up
+LargeArgs large_in(const char *const *d_src, const int *d_srcSize, char *const *d_dst,
+                   const int *d_dstCap, int *d_result, int nblocks, int maxSrcSize,
+                   void *d_scratch, int restartBytes = 0, void *d_index = nullptr,
+                   size_t index_stride = 0) {
+    LargeArgs a{};
+    a.restart = restartBytes;
+    a.index = (char *)d_index;
+    a.index_stride = index_stride;
+    a.src = d_src;
+    a.src_size = d_srcSize;
+    a.dst = d_dst;
+    a.dst_cap = d_dstCap;
+    a.result = d_result;
+    a.nblocks = nblocks;
+    a.max_src = maxSrcSize;
+    a.buf = (char *)d_scratch;
+    return a;
+}
+
+int check_large_arrays(const char *who, const LargeArgs &a) {
+    return check_arrays(who, a.nblocks, {a.src, a.src_size, a.dst, a.dst_cap, a.result, a.buf});
+}
+
+// what compress_large and compress_large_hc ask of maxSrcSize, restartBytes and the index
+int check_large(const char *who, const LargeArgs &a) {
+    if (!large_src_ok(a.max_src))
+        return einval("%s: maxSrcSize %d outside [1, %d]", who, a.max_src, kLargeMaxSrc);
+    if (!restart_ok(a.restart))
+        return einval("%s: restartBytes %d is neither 0 nor a positive multiple of the slice size "
+                      "%d", who, a.restart, large_slice_size());
+    const size_t least = large_index_size(a.max_src, a.restart);
+    if (a.index && (!aligned16(a.index) || a.index_stride % 16u || a.index_stride < least))
+        return einval("%s: index at %p with stride %zu, need 16-byte alignment and a stride that "
+                      "is a multiple of 16 and >= %zu", who, a.index, a.index_stride, least);
+    return APE_LZ4_GPU_OK;
+}
+
+// cut the scratch of a batch that has blocks into the slot arrays; it has to hold them and
+// `tables` more bytes, which then begin at *base
+int large_layout(const char *who, LargeArgs &a, size_t scratch_bytes, size_t tables,
+                 size_t *base) {
+    const char *scratch = a.buf;
+    *base = up16(large_scratch_layout(a.nblocks, a.max_src, &a));
+    if (*base == 0)
+        return einval("%s: %d inputs of up to %d bytes are more slices than one call takes; "
+                      "split the batch", who, a.nblocks, a.max_src);
+    if (scratch_bytes < *base + tables || !aligned16(scratch))
+        return einval("%s: scratch of %zu bytes at %p, need %zu bytes 16-byte aligned", who,
+                      scratch_bytes, scratch, *base + tables);
+    return APE_LZ4_GPU_OK;
+}
+
+// The scratch is looked at only once there is work to do, so after the device check: an empty
+// batch is OK with any scratch.
+int large_batch(const char *who, LargeArgs a, int acceleration, size_t scratch_bytes,
+                void *stream, hipEvent_t *ev) {
+    if (int rc = check_large_arrays(who, a)) return rc;
+    if (int rc = check_large(who, a)) return rc;
+    if (int rc = check_device()) return rc;
+    if (a.nblocks == 0) return APE_LZ4_GPU_OK;
+    size_t need = 0;
+    if (int rc = large_layout(who, a, scratch_bytes, 0, &need)) return rc;
+    return finish_launch(launch_large(a, acceleration, (hipStream_t)stream, ev),
+                         "large plan + lz4_encode_kernel + offsets + stitch");
+}
+
+// ---- the high-ratio mode on inputs of any size (lz4_large.hip launch_large_hc) ----
+// Scratch: the large path's layout, then the chain and match tables of one pass of slices.
+// slices per pass out of `want` (0 = all): 1 .. min(slots, kHcSub)
+int large_hc_pass(long long nslots, long long want) {
+    long long most = nslots < kHcSub ? nslots : kHcSub;
+    if (most < 1) most = 1;
+    if (want <= 0 || want > most) want = most;
+    return (int)want;
+}
+
+size_t large_hc_scratch(int nblocks, int maxSrcSize, int passSlices, size_t slot) {
+    if (nblocks < 0 || !large_src_ok(maxSrcSize) || passSlices < 0) return 0;
+    const size_t base = large_scratch_layout(nblocks, maxSrcSize, nullptr);
+    if (!base) return (size_t)-1;   // more slice slots than one call takes: split the batch
+    const long long S = large_slice_size();
+    const long long nsl = maxSrcSize <= kMaxBlock ? 1 : ((long long)maxSrcSize + S - 1) / S;
+    return up16(base) + (size_t)large_hc_pass(nblocks * nsl, passSlices) * slot;
+}
+
+// Unlike large_batch, the scratch of a batch that has blocks is checked before the device.
+// ms6 (nullable): the timed form.
+int large_hc_batch(const char *who, bool opt, LargeArgs a, int depth, size_t scratch_bytes,
+                   void *stream, float *ms6) {
+    const size_t slot = opt ? kHcOptSlotBytes : kHcSlotBytes;
+    char *const scratch = a.buf;
+    if (int rc = check_large_arrays(who, a)) return rc;
+    if (depth < 0 || depth > kHcMaxDepth)
+        return einval("%s: depth %d outside 0..%d", who, depth, kHcMaxDepth);
+    if (int rc = check_large(who, a)) return rc;
+    size_t base = 0;
+    if (a.nblocks > 0)
+        if (int rc = large_layout(who, a, scratch_bytes, slot, &base)) return rc;
+    if (int rc = check_device()) return rc;
+    if (a.nblocks == 0) return APE_LZ4_GPU_OK;
+    // as many slices per pass as the caller's scratch holds
+    const int pass = large_hc_pass(a.nslots, (long long)((scratch_bytes - base) / slot));
+    const char *what = "large plan + lz4_hc kernels + offsets + stitch";
+    const hipStream_t s = (hipStream_t)stream;
+    const int d = depth ? depth : kHcDefaultDepth;
+    if (!ms6)
+        return finish_launch(launch_large_hc(a, d, scratch + base, pass, s, nullptr, opt), what);
+    // the timed form: events around every launch, the passes' times summed per kernel
+    const int passes = large_hc_passes(a.nslots, pass);
+    Events t(5 + 3 * passes);
+    int rc = t.create();
+    if (rc == APE_LZ4_GPU_OK)
+        rc = finish_launch(launch_large_hc(a, d, scratch + base, pass, s, t.ev.data(), opt), what);
+    for (int q = 0; q < 6; q++) ms6[q] = 0.f;
+    if (rc == APE_LZ4_GPU_OK) {
+        hipError_t e = hipEventSynchronize(t.ev.back());
+        auto span = [&](int slot, int from) {
+            float ms = 0.f;
+            if (e == hipSuccess) e = hipEventElapsedTime(&ms, t.ev[from], t.ev[from + 1]);
+            ms6[slot] += ms;
+        };
+        span(0, 0);
+        for (int p = 0; p < passes; p++)
+            for (int k = 0; k < 3; k++) span(1 + k, 1 + 3 * p + k);
+        span(4, 1 + 3 * passes);
+        span(5, 2 + 3 * passes);   // (the index launch, after it, is not in any figure)
+        rc = finish_launch(e, "compress_large_hc stage events");
+    }
+    return rc;
+}
+
+// ---- indexed blocks (lz4_decode.hip) ----
+// the stride holds the header and maxSegments + 1 pairs, so a block's index is never read past
+bool index_ok(const void *d_index, size_t index_stride, int maxSegments) {
+    return maxSegments >= 1 && aligned16(d_index) && index_stride % 16u == 0 &&
+           index_stride >= 16u + 8u * ((size_t)maxSegments + 1u);
+}
+
 }  // namespace
 
+extern "C" {
+
+int APE_LZ4_gpu_init(void) { return check_device(); }
+
+int APE_LZ4_gpu_device_count(void) {
+    std::call_once(g_once, probe);
+    return g_ndev < 0 ? 0 : g_ndev;
+}
+
+const char *APE_LZ4_gpu_last_error(void) { return g_err; }
+const char *APE_LZ4_gpu_arch(void) { return "gfx950"; }
+
+int APE_LZ4_compress_batch_dev(const char *const *d_src, const int *d_srcSize,
+                               char *const *d_dst, const int *d_dstCap, int *d_result,
+                               int nblocks, void *stream) {
+    BlockArgs a = ptr_args(d_src, d_srcSize, d_dst, d_dstCap, nullptr, d_result, nblocks);
+    if (int rc = ready_ptr("compress_batch_dev", a)) return rc;
+    return finish_launch(launch_encode(a, (hipStream_t)stream), "lz4_encode_kernel");
+}
+
+int APE_LZ4_compress_fast_batch_dev(const char *const *d_src, const int *d_srcSize,
+                                    char *const *d_dst, const int *d_dstCap, int *d_result,
+                                    int nblocks, int acceleration, void *stream) {
+    BlockArgs a = ptr_args(d_src, d_srcSize, d_dst, d_dstCap, nullptr, d_result, nblocks);
+    a.accel = acceleration;
+    if (int rc = ready_ptr("compress_fast_batch_dev", a)) return rc;
+    return finish_launch(launch_encode(a, (hipStream_t)stream), "lz4_encode_kernel");
+}
+
+int APE_LZ4_compress_exact_batch_dev(const char *const *d_src, const int *d_srcSize,
+                                     char *const *d_dst, const int *d_dstCap, int *d_result,
+                                     int nblocks, int acceleration, void *stream) {
+    BlockArgs a = ptr_args(d_src, d_srcSize, d_dst, d_dstCap, nullptr, d_result, nblocks);
+    a.accel = acceleration;
+    if (int rc = ready_ptr("compress_exact_batch_dev", a)) return rc;
+    return finish_launch(launch_encode_exact(a, (hipStream_t)stream), "lz4_encode_exact_kernel");
+}
+
+int APE_LZ4_decompress_safe_batch_dev(const char *const *d_src, const int *d_compressedSize,
+                                      char *const *d_dst, const int *d_maxDecompressedSize,
+                                      int *d_result, int nblocks, void *stream) {
+    BlockArgs a = ptr_args(d_src, d_compressedSize, d_dst, d_maxDecompressedSize, nullptr,
+                           d_result, nblocks);
+    if (int rc = ready_ptr("decompress_safe_batch_dev", a)) return rc;
+    return finish_launch(launch_decode(a, false, (hipStream_t)stream), "lz4_decode_kernel");
+}
+
+int APE_LZ4_decompress_safe_partial_batch_dev(const char *const *d_src,
+                                              const int *d_compressedSize, char *const *d_dst,
+                                              const int *d_targetOutputSize,
+                                              const int *d_maxDecompressedSize, int *d_result,
+                                              int nblocks, void *stream) {
+    BlockArgs a = ptr_args(d_src, d_compressedSize, d_dst, d_maxDecompressedSize,
+                           d_targetOutputSize, d_result, nblocks);
+    if (int rc = ready_ptr("decompress_safe_partial_batch_dev", a, {d_targetOutputSize}))
+        return rc;
+    return finish_launch(launch_decode(a, true, (hipStream_t)stream),
+                         "lz4_decode_kernel<partial>");
+}
+
+int APE_LZ4_decompress_safe_usingDict_batch_dev(const char *const *d_src,
+                                                const int *d_compressedSize, char *const *d_dst,
+                                                const int *d_maxDecompressedSize,
+                                                const char *const *d_dict, const int *d_dictSize,
+                                                int *d_result, int nblocks, void *stream) {
+    BlockArgs a = ptr_args(d_src, d_compressedSize, d_dst, d_maxDecompressedSize, nullptr,
+                           d_result, nblocks);
+    a.dict = d_dict;
+    a.dict_size = d_dictSize;
+    if (int rc = ready_ptr("decompress_safe_usingDict_batch_dev", a, {d_dict, d_dictSize}))
+        return rc;
+    return finish_launch(launch_decode(a, false, (hipStream_t)stream),
+                         "lz4_decode_kernel<usingDict>");
+}
+
+int APE_LZ4_decompress_fast_batch_dev(const char *const *d_src, const int *d_srcBound,
+                                      char *const *d_dst, const int *d_originalSize,
+                                      int *d_result, int nblocks, void *stream) {
+    BlockArgs a = ptr_args(d_src, d_srcBound, d_dst, d_originalSize, nullptr, d_result, nblocks);
+    a.fast = 1;
+    if (int rc = ready_ptr("decompress_fast_batch_dev", a)) return rc;
+    return finish_launch(launch_decode(a, false, (hipStream_t)stream), "lz4_decode_kernel<fast>");
+}
+
+int APE_LZ4_compress_withPrefix_batch_dev(const char *const *d_src, const int *d_srcSize,
+                                          const int *d_prefixSize, char *const *d_dst,
+                                          const int *d_dstCap, int *d_result, int nblocks,
+                                          void *stream) {
+    BlockArgs a = ptr_args(d_src, d_srcSize, d_dst, d_dstCap, nullptr, d_result, nblocks);
+    a.dict_size = d_prefixSize;
+    if (int rc = ready_ptr("compress_withPrefix_batch_dev", a, {d_prefixSize})) return rc;
+    return finish_launch(launch_encode(a, (hipStream_t)stream), "lz4_encode_kernel<prefix>");
+}
+
+// ---- prepared dictionaries (lz4_cdict.hip, the encoder's EXT instantiation) ----
+size_t APE_LZ4_cdict_size(void) { return (size_t)kCdSize; }
+
+int APE_LZ4_cdict_window(int dictSize, int maxSrcSize) {
+    if (dictSize < 0 || maxSrcSize < 1 || maxSrcSize > kMaxBlock) return -1;
+    const int D = cdict_window(dictSize, maxSrcSize);
+    return D < 64 ? 0 : D;
+}
+
+int APE_LZ4_cdict_prepare_dev(const char *d_dict, int dictSize, int maxSrcSize, void *d_cdict,
+                              size_t cdict_bytes, void *stream) {
+    if (int rc = ready_prepare("cdict_prepare_dev", d_dict, dictSize, maxSrcSize, d_cdict,
+                               cdict_bytes, kCdSize))
+        return rc;
+    return finish_launch(launch_cdict_prepare(d_dict, dictSize, maxSrcSize, d_cdict,
+                                              (hipStream_t)stream),
+                         "lz4_cdict_prepare_kernel");
+}
+
+// (the object is needed for an empty batch too)
+int APE_LZ4_compress_usingCDict_batch_dev(const char *const *d_src, const int *d_srcSize,
+                                          char *const *d_dst, const int *d_dstCap, int *d_result,
+                                          int nblocks, const void *d_cdict, void *stream) {
+    if (!d_cdict || !aligned16(d_cdict))
+        return einval("compress_usingCDict_batch_dev: object at %p, need one 16-byte aligned",
+                      d_cdict);
+    BlockArgs a = ptr_args(d_src, d_srcSize, d_dst, d_dstCap, nullptr, d_result, nblocks);
+    if (int rc = ready_ptr("compress_usingCDict_batch_dev", a)) return rc;
+    return finish_launch(launch_encode_cdict(a, d_cdict, (hipStream_t)stream),
+                         "lz4_encode_cdict_kernel");
+}
+
+// ---- compress_destSize (lz4_destsize.hip) ----
 size_t APE_LZ4_compress_destSize_scratch_size(int nblocks) {
     const int sub = nblocks < 1 ? 1 : (nblocks < kDsSub ? nblocks : kDsSub);
     return ds_scratch(sub);
 }
 
+// (the scratch's size and alignment are looked at only once there is work to do, so after the
+// device check: an empty batch is OK with any scratch)
 int APE_LZ4_compress_destSize_batch_scratch_dev(const char *const *d_src, int *d_srcSize,
                                                 char *const *d_dst, const int *d_targetDstSize,
                                                 int *d_result, int nblocks, void *d_scratch,
                                                 size_t scratch_bytes, void *stream) {
-    if (nblocks < 0 || (nblocks > 0 && (!d_src || !d_srcSize || !d_dst || !d_targetDstSize ||
-                                         !d_result || !d_scratch)))
-        return APE_LZ4_GPU_EINVAL;
-    int rc = check_device();
-    if (rc) return rc;
+    const char *who = "compress_destSize_batch_scratch_dev";
+    if (int rc = check_arrays(who, nblocks,
+                              {d_src, d_srcSize, d_dst, d_targetDstSize, d_result, d_scratch}))
+        return rc;
+    if (int rc = check_device()) return rc;
     if (nblocks == 0) return APE_LZ4_GPU_OK;
-    // as many blocks per pass as the caller's scratch holds (at least one)
-    int sub = (int)(scratch_bytes / (ds_stride() + sizeof(int)));
-    if (sub < 1) {
-        snprintf(g_err, sizeof g_err, "destSize scratch of %zu bytes < %zu (one block)",
-                 scratch_bytes, ds_scratch(1));
-        return APE_LZ4_GPU_EINVAL;
-    }
-    if (sub > nblocks) sub = nblocks;
-    if ((uintptr_t)d_scratch & 15u) return APE_LZ4_GPU_EINVAL;
+    if (scratch_bytes < ds_scratch(1))
+        return einval("%s: destSize scratch of %zu bytes < %zu (one block)", who, scratch_bytes,
+                      ds_scratch(1));
+    if (!aligned16(d_scratch))
+        return einval("%s: scratch at %p is not 16-byte aligned", who, d_scratch);
+    const int sub = pass_blocks(scratch_bytes, ds_scratch(1), nblocks, nblocks);
     return finish_launch(destsize_passes(d_src, d_srcSize, d_dst, d_targetDstSize, d_result,
                                          nblocks, (char *)d_scratch, sub, (hipStream_t)stream),
                          "lz4_encode_kernel + lz4_destsize_kernel");
@@ -491,11 +788,10 @@ int APE_LZ4_compress_destSize_batch_scratch_dev(const char *const *d_src, int *d
 int APE_LZ4_compress_destSize_batch_dev(const char *const *d_src, int *d_srcSize,
                                         char *const *d_dst, const int *d_targetDstSize,
                                         int *d_result, int nblocks, void *stream) {
-    if (nblocks < 0 || (nblocks > 0 && (!d_src || !d_srcSize || !d_dst || !d_targetDstSize ||
-                                         !d_result)))
-        return APE_LZ4_GPU_EINVAL;
-    int rc = check_device();
-    if (rc) return rc;
+    if (int rc = check_arrays("compress_destSize_batch_dev", nblocks,
+                              {d_src, d_srcSize, d_dst, d_targetDstSize, d_result}))
+        return rc;
+    if (int rc = check_device()) return rc;
     if (nblocks == 0) return APE_LZ4_GPU_OK;
     // The one launcher that allocates: stream-ordered scratch (hipMallocAsync / hipFreeAsync
     // on the caller's stream, so concurrent calls never share it).  Under graph capture
@@ -515,10 +811,6 @@ int APE_LZ4_compress_destSize_batch_dev(const char *const *d_src, int *d_srcSize
 }
 
 // ---- the high-ratio mode (lz4_encode_hc.hip) ----
-namespace {
-constexpr int kHcSub = 1024;   // blocks per scratch pass: 262144 search workgroups
-}
-
 size_t APE_LZ4_compress_hc_scratch_size(int nblocks) {
     if (nblocks <= 0) return 0;
     return (size_t)(nblocks < kHcSub ? nblocks : kHcSub) * kHcSlotBytes;
@@ -529,62 +821,12 @@ size_t APE_LZ4_compress_hc_opt_scratch_size(int nblocks) {
     return (size_t)(nblocks < kHcSub ? nblocks : kHcSub) * kHcOptSlotBytes;
 }
 
-namespace {
-// d_prefixSize (nullable): per-block bytes of history before d_src[i]; opt: the cost-minimising
-// parse (lz4_encode_hc.hip), whose cost tables follow the match tables in the scratch
-int hc_batch(const char *what, bool opt, const char *const *d_src, const int *d_srcSize,
-             const int *d_prefixSize, char *const *d_dst, const int *d_dstCap, int *d_result,
-             int nblocks, int depth, void *d_scratch, size_t scratch_bytes, void *stream) {
-    const size_t slot = opt ? kHcOptSlotBytes : kHcSlotBytes;
-    if (nblocks < 0 || depth < 0 || depth > kHcMaxDepth || !d_scratch ||
-        ((uintptr_t)d_scratch & 15u) || scratch_bytes < slot ||
-        (nblocks > 0 && (!d_src || !d_srcSize || !d_dst || !d_dstCap || !d_result))) {
-        snprintf(g_err, sizeof g_err, "%s: nblocks %d, depth %d (0..%d), scratch of %zu "
-                 "bytes at %p (need %zu bytes, 16-byte aligned)", what, nblocks, depth,
-                 kHcMaxDepth, scratch_bytes, d_scratch, slot);
-        return APE_LZ4_GPU_EINVAL;
-    }
-    int rc = check_device();
-    if (rc) return rc;
-    // as many blocks per pass as the caller's scratch holds
-    const size_t fit = scratch_bytes / slot;
-    int sub = fit < (size_t)kHcSub ? (int)fit : kHcSub;
-    if (sub > nblocks) sub = nblocks;
-    hipError_t e = hipSuccess;
-    for (int off = 0; off < nblocks && e == hipSuccess; off += sub) {
-        HcArgs a{};
-        a.src = d_src + off;
-        a.src_size = d_srcSize + off;
-        a.dst = d_dst + off;
-        a.dst_cap = d_dstCap + off;
-        a.result = d_result + off;
-        a.prefix = d_prefixSize ? d_prefixSize + off : nullptr;
-        a.nblocks = nblocks - off < sub ? nblocks - off : sub;
-        a.depth = depth ? depth : kHcDefaultDepth;
-        a.chain = (uint16_t *)d_scratch;
-        a.match = (uint32_t *)((char *)d_scratch + (size_t)sub * kHcChainBytes);
-        if (opt) {
-            HcOptArgs o{};
-            o.a = a;
-            o.cost = (uint32_t *)((char *)d_scratch + (size_t)sub * kHcSlotBytes);
-            e = launch_encode_hc_opt(o, (hipStream_t)stream);
-        } else {
-            e = launch_encode_hc(a, (hipStream_t)stream);
-        }
-    }
-    return finish_launch(e, opt ? "lz4_hc_chain_kernel + lz4_hc_search_kernel + "
-                                  "lz4_hc_opt_parse_kernel"
-                                : "lz4_hc_chain_kernel + lz4_hc_search_kernel + "
-                                  "lz4_hc_parse_kernel");
-}
-}  // namespace
-
 int APE_LZ4_compress_hc_opt_batch_dev(const char *const *d_src, const int *d_srcSize,
                                       char *const *d_dst, const int *d_dstCap, int *d_result,
                                       int nblocks, int depth, void *d_scratch,
                                       size_t scratch_bytes, void *stream) {
-    return hc_batch("compress_hc_opt", true, d_src, d_srcSize, nullptr, d_dst, d_dstCap, d_result,
-                    nblocks, depth, d_scratch, scratch_bytes, stream);
+    return hc_batch("compress_hc_opt_batch_dev", true, d_src, d_srcSize, nullptr, d_dst, d_dstCap,
+                    d_result, nblocks, depth, d_scratch, scratch_bytes, stream);
 }
 
 int APE_LZ4_compress_hc_opt_withPrefix_batch_dev(const char *const *d_src, const int *d_srcSize,
@@ -592,16 +834,16 @@ int APE_LZ4_compress_hc_opt_withPrefix_batch_dev(const char *const *d_src, const
                                                  const int *d_dstCap, int *d_result, int nblocks,
                                                  int depth, void *d_scratch, size_t scratch_bytes,
                                                  void *stream) {
-    return hc_batch("compress_hc_opt_withPrefix", true, d_src, d_srcSize, d_prefixSize, d_dst,
-                    d_dstCap, d_result, nblocks, depth, d_scratch, scratch_bytes, stream);
+    return hc_batch("compress_hc_opt_withPrefix_batch_dev", true, d_src, d_srcSize, d_prefixSize,
+                    d_dst, d_dstCap, d_result, nblocks, depth, d_scratch, scratch_bytes, stream);
 }
 
 int APE_LZ4_compress_hc_batch_dev(const char *const *d_src, const int *d_srcSize,
                                   char *const *d_dst, const int *d_dstCap, int *d_result,
                                   int nblocks, int depth, void *d_scratch, size_t scratch_bytes,
                                   void *stream) {
-    return hc_batch("compress_hc", false, d_src, d_srcSize, nullptr, d_dst, d_dstCap, d_result,
-                    nblocks, depth, d_scratch, scratch_bytes, stream);
+    return hc_batch("compress_hc_batch_dev", false, d_src, d_srcSize, nullptr, d_dst, d_dstCap,
+                    d_result, nblocks, depth, d_scratch, scratch_bytes, stream);
 }
 
 int APE_LZ4_compress_hc_withPrefix_batch_dev(const char *const *d_src, const int *d_srcSize,
@@ -609,8 +851,8 @@ int APE_LZ4_compress_hc_withPrefix_batch_dev(const char *const *d_src, const int
                                              const int *d_dstCap, int *d_result, int nblocks,
                                              int depth, void *d_scratch, size_t scratch_bytes,
                                              void *stream) {
-    return hc_batch("compress_hc_withPrefix", false, d_src, d_srcSize, d_prefixSize, d_dst,
-                    d_dstCap, d_result, nblocks, depth, d_scratch, scratch_bytes, stream);
+    return hc_batch("compress_hc_withPrefix_batch_dev", false, d_src, d_srcSize, d_prefixSize,
+                    d_dst, d_dstCap, d_result, nblocks, depth, d_scratch, scratch_bytes, stream);
 }
 
 // ---- the high-ratio mode against a prepared dictionary (lz4_hc_cdict.hip) ----
@@ -623,107 +865,30 @@ int APE_LZ4_hc_cdict_window(int dictSize, int maxSrcSize) {
 
 int APE_LZ4_hc_cdict_prepare_dev(const char *d_dict, int dictSize, int maxSrcSize, void *d_cdict,
                                  size_t cdict_bytes, void *stream) {
-    if (dictSize < 0 || (dictSize > 0 && !d_dict) || maxSrcSize < 1 || maxSrcSize > kMaxBlock ||
-        !d_cdict || cdict_bytes < (size_t)kHdSize || ((uintptr_t)d_cdict & 15u)) {
-        snprintf(g_err, sizeof g_err, "hc_cdict_prepare: dictSize %d, maxSrcSize %d (1..%d), "
-                 "object of %zu bytes at %p (need %u bytes, 16-byte aligned)", dictSize,
-                 maxSrcSize, kMaxBlock, cdict_bytes, d_cdict, kHdSize);
-        return APE_LZ4_GPU_EINVAL;
-    }
-    int rc = check_device();
-    if (rc) return rc;
+    if (int rc = ready_prepare("hc_cdict_prepare_dev", d_dict, dictSize, maxSrcSize, d_cdict,
+                               cdict_bytes, kHdSize))
+        return rc;
     return finish_launch(launch_hc_cdict_prepare(d_dict, dictSize, maxSrcSize, d_cdict,
                                                  (hipStream_t)stream),
                          "lz4_hc_cdict_prepare_kernel");
 }
 
-namespace {
-// messages per scratch pass: as many as make kHcSub x 256 search workgroups
-inline int hc_cdict_sub(int maxSrcSize) {
-    return kHcSub * (kMaxBlock / kHcdThreads) / hc_cdict_groups(maxSrcSize);
-}
-}  // namespace
-
 size_t APE_LZ4_compress_hc_usingCDict_scratch_size(int nblocks, int maxSrcSize) {
-    if (nblocks <= 0 || maxSrcSize < 1 || maxSrcSize > kMaxBlock) return 0;
-    const int sub = hc_cdict_sub(maxSrcSize);
-    return (size_t)(nblocks < sub ? nblocks : sub) * hc_cdict_slot_bytes(maxSrcSize);
+    return hc_cdict_scratch(nblocks, maxSrcSize, false);
 }
 
 size_t APE_LZ4_compress_hc_opt_usingCDict_scratch_size(int nblocks, int maxSrcSize) {
-    if (nblocks <= 0 || maxSrcSize < 1 || maxSrcSize > kMaxBlock) return 0;
-    const int sub = hc_cdict_sub(maxSrcSize);
-    return (size_t)(nblocks < sub ? nblocks : sub) * hc_cdict_opt_slot_bytes(maxSrcSize);
+    return hc_cdict_scratch(nblocks, maxSrcSize, true);
 }
-
-namespace {
-// opt: the cost-minimising parse (lz4_hc_cdict_opt_parse_kernel), whose cost tables follow the
-// match tables in the scratch
-int hc_cdict_batch(const char *what, bool opt, const char *const *d_src, const int *d_srcSize,
-                   char *const *d_dst, const int *d_dstCap, int *d_result, int nblocks,
-                   const void *d_cdict, int maxSrcSize, int depth, void *d_scratch,
-                   size_t scratch_bytes, void *stream) {
-    const bool range = maxSrcSize >= 1 && maxSrcSize <= kMaxBlock;
-    const size_t slot = !range ? 0 : opt ? hc_cdict_opt_slot_bytes(maxSrcSize)
-                                         : hc_cdict_slot_bytes(maxSrcSize);
-    if (nblocks < 0 || !range || depth < 0 || depth > kHcMaxDepth || !d_cdict ||
-        ((uintptr_t)d_cdict & 15u) || !d_scratch || ((uintptr_t)d_scratch & 15u) ||
-        scratch_bytes < slot ||
-        (nblocks > 0 && (!d_src || !d_srcSize || !d_dst || !d_dstCap || !d_result))) {
-        snprintf(g_err, sizeof g_err, "%s: nblocks %d, maxSrcSize %d (1..%d), "
-                 "depth %d (0..%d), object at %p, scratch of %zu bytes at %p (need %zu bytes; "
-                 "both 16-byte aligned)", what, nblocks, maxSrcSize, kMaxBlock, depth, kHcMaxDepth,
-                 d_cdict, scratch_bytes, d_scratch, slot);
-        return APE_LZ4_GPU_EINVAL;
-    }
-    int rc = check_device();
-    if (rc) return rc;
-    // as many messages per pass as the caller's scratch holds
-    const size_t fit = scratch_bytes / slot;
-    int sub = hc_cdict_sub(maxSrcSize);
-    if (fit < (size_t)sub) sub = (int)fit;
-    if (sub > nblocks) sub = nblocks;
-    hipError_t e = hipSuccess;
-    for (int off = 0; off < nblocks && e == hipSuccess; off += sub) {
-        HcDictArgs a{};
-        a.src = d_src + off;
-        a.src_size = d_srcSize + off;
-        a.dst = d_dst + off;
-        a.dst_cap = d_dstCap + off;
-        a.result = d_result + off;
-        a.nblocks = nblocks - off < sub ? nblocks - off : sub;
-        a.depth = depth ? depth : kHcDefaultDepth;
-        a.max_src = maxSrcSize;
-        a.cdict = (const uint8_t *)d_cdict;
-        a.chain_stride = (uint32_t)hc_cdict_chain_entries(maxSrcSize);
-        a.match_stride = (uint32_t)hc_cdict_match_entries(maxSrcSize);
-        a.chain = (uint16_t *)d_scratch;
-        a.match = (uint32_t *)((char *)d_scratch + (size_t)sub * a.chain_stride * sizeof(uint16_t));
-        if (opt) {
-            HcDictOptArgs o{};
-            o.a = a;
-            o.cost_stride = (uint32_t)hc_cdict_cost_entries(maxSrcSize);
-            o.cost = (uint32_t *)((char *)d_scratch + (size_t)sub * hc_cdict_slot_bytes(maxSrcSize));
-            e = launch_encode_hc_cdict_opt(o, (hipStream_t)stream);
-        } else {
-            e = launch_encode_hc_cdict(a, (hipStream_t)stream);
-        }
-    }
-    return finish_launch(e, opt ? "lz4_hc_cdict_chain_kernel + lz4_hc_cdict_search_kernel + "
-                                  "lz4_hc_cdict_opt_parse_kernel"
-                                : "lz4_hc_cdict_chain_kernel + lz4_hc_cdict_search_kernel + "
-                                  "lz4_hc_cdict_parse_kernel");
-}
-}  // namespace
 
 int APE_LZ4_compress_hc_usingCDict_batch_dev(const char *const *d_src, const int *d_srcSize,
                                              char *const *d_dst, const int *d_dstCap,
                                              int *d_result, int nblocks, const void *d_cdict,
                                              int maxSrcSize, int depth, void *d_scratch,
                                              size_t scratch_bytes, void *stream) {
-    return hc_cdict_batch("compress_hc_usingCDict", false, d_src, d_srcSize, d_dst, d_dstCap,
-                          d_result, nblocks, d_cdict, maxSrcSize, depth, d_scratch, scratch_bytes,
-                          stream);
+    return hc_cdict_batch("compress_hc_usingCDict_batch_dev", false, d_src, d_srcSize, d_dst,
+                          d_dstCap, d_result, nblocks, d_cdict, maxSrcSize, depth, d_scratch,
+                          scratch_bytes, stream);
 }
 
 int APE_LZ4_compress_hc_opt_usingCDict_batch_dev(const char *const *d_src, const int *d_srcSize,
@@ -731,43 +896,38 @@ int APE_LZ4_compress_hc_opt_usingCDict_batch_dev(const char *const *d_src, const
                                                  int *d_result, int nblocks, const void *d_cdict,
                                                  int maxSrcSize, int depth, void *d_scratch,
                                                  size_t scratch_bytes, void *stream) {
-    return hc_cdict_batch("compress_hc_opt_usingCDict", true, d_src, d_srcSize, d_dst, d_dstCap,
-                          d_result, nblocks, d_cdict, maxSrcSize, depth, d_scratch, scratch_bytes,
-                          stream);
+    return hc_cdict_batch("compress_hc_opt_usingCDict_batch_dev", true, d_src, d_srcSize, d_dst,
+                          d_dstCap, d_result, nblocks, d_cdict, maxSrcSize, depth, d_scratch,
+                          scratch_bytes, stream);
 }
 
 // ---- inputs of any size as one block (lz4_large.hip) ----
-namespace {
-constexpr int kLargeMaxSrc = 0x7E000000;   // LZ4_MAX_INPUT_SIZE (ref src/ape_lz4.h)
-}
-
 int APE_LZ4_compress_large_slice_size(void) { return large_slice_size(); }
 
 size_t APE_LZ4_compress_large_scratch_size(int nblocks, int maxSrcSize) {
-    if (nblocks < 0 || maxSrcSize < 1 || maxSrcSize > kLargeMaxSrc) return 0;
+    if (nblocks < 0 || !large_src_ok(maxSrcSize)) return 0;
     const size_t need = large_scratch_layout(nblocks, maxSrcSize, nullptr);
     return need ? need : (size_t)-1;   // more slice slots than one call takes: split the batch
 }
 
-namespace {
-int large_batch(const char *const *d_src, const int *d_srcSize, char *const *d_dst,
-                const int *d_dstCap, int *d_result, int nblocks, int maxSrcSize, int acceleration,
-                void *d_scratch, size_t scratch_bytes, void *stream, hipEvent_t *ev,
-                int restartBytes = 0, void *d_index = nullptr, size_t index_stride = 0);
-// restartBytes: 0 or a positive multiple of the slice size
-bool restart_ok(int restartBytes) {
-    return restartBytes >= 0 && restartBytes % large_slice_size() == 0;
-}
-}
-
 int APE_LZ4_large_index_segments(int maxSrcSize, int restartBytes) {
-    if (maxSrcSize < 1 || maxSrcSize > kLargeMaxSrc || !restart_ok(restartBytes)) return 0;
+    if (!large_src_ok(maxSrcSize) || !restart_ok(restartBytes)) return 0;
     return (int)large_index_segments(maxSrcSize, restartBytes);
 }
 
 size_t APE_LZ4_large_index_size(int maxSrcSize, int restartBytes) {
-    if (maxSrcSize < 1 || maxSrcSize > kLargeMaxSrc || !restart_ok(restartBytes)) return 0;
+    if (!large_src_ok(maxSrcSize) || !restart_ok(restartBytes)) return 0;
     return large_index_size(maxSrcSize, restartBytes);
+}
+
+int APE_LZ4_compress_large_batch_dev(const char *const *d_src, const int *d_srcSize,
+                                     char *const *d_dst, const int *d_dstCap, int *d_result,
+                                     int nblocks, int maxSrcSize, int acceleration,
+                                     void *d_scratch, size_t scratch_bytes, void *stream) {
+    return large_batch("compress_large_batch_dev",
+                       large_in(d_src, d_srcSize, d_dst, d_dstCap, d_result, nblocks, maxSrcSize,
+                                d_scratch),
+                       acceleration, scratch_bytes, stream, nullptr);
 }
 
 int APE_LZ4_compress_large_indexed_batch_dev(const char *const *d_src, const int *d_srcSize,
@@ -776,9 +936,35 @@ int APE_LZ4_compress_large_indexed_batch_dev(const char *const *d_src, const int
                                              int acceleration, void *d_scratch,
                                              size_t scratch_bytes, int restartBytes, void *d_index,
                                              size_t index_stride, void *stream) {
-    return large_batch(d_src, d_srcSize, d_dst, d_dstCap, d_result, nblocks, maxSrcSize,
-                       acceleration, d_scratch, scratch_bytes, stream, nullptr, restartBytes,
-                       d_index, index_stride);
+    return large_batch("compress_large_indexed_batch_dev",
+                       large_in(d_src, d_srcSize, d_dst, d_dstCap, d_result, nblocks, maxSrcSize,
+                                d_scratch, restartBytes, d_index, index_stride),
+                       acceleration, scratch_bytes, stream, nullptr);
+}
+
+// (the events are made before the arguments are looked at, so without a device the call fails
+// there)
+int APE_LZ4_compress_large_timed_dev(const char *const *d_src, const int *d_srcSize,
+                                     char *const *d_dst, const int *d_dstCap, int *d_result,
+                                     int nblocks, int maxSrcSize, int acceleration,
+                                     void *d_scratch, size_t scratch_bytes, void *stream,
+                                     float *ms4) {
+    if (!ms4) return einval("compress_large_timed_dev: ms4 is null");
+    Events t(5);
+    int rc = t.create();
+    if (rc == APE_LZ4_GPU_OK)
+        rc = large_batch("compress_large_timed_dev",
+                         large_in(d_src, d_srcSize, d_dst, d_dstCap, d_result, nblocks, maxSrcSize,
+                                  d_scratch),
+                         acceleration, scratch_bytes, stream, t.ev.data());
+    for (int q = 0; q < 4; q++) ms4[q] = 0.f;
+    if (rc == APE_LZ4_GPU_OK && nblocks > 0) {
+        hipError_t e = hipEventSynchronize(t.ev[4]);
+        for (int q = 0; q < 4 && e == hipSuccess; q++)
+            e = hipEventElapsedTime(&ms4[q], t.ev[q], t.ev[q + 1]);
+        rc = finish_launch(e, "compress_large stage events");
+    }
+    return rc;
 }
 
 int APE_LZ4_decompress_safe_indexed_batch_dev(const char *const *d_src,
@@ -787,24 +973,18 @@ int APE_LZ4_decompress_safe_indexed_batch_dev(const char *const *d_src,
                                               const void *d_index, size_t index_stride,
                                               int maxSegments, int *d_result, int nblocks,
                                               void *stream) {
-    if (nblocks < 0 || (nblocks > 0 && (!d_src || !d_compressedSize || !d_dst ||
-                                         !d_maxDecompressedSize || !d_index || !d_result))) {
-        snprintf(g_err, sizeof g_err, "invalid argument");
-        return APE_LZ4_GPU_EINVAL;
-    }
-    // one wave per (block, segment) in a one-dimensional grid; the stride holds the header
-    // and maxSegments + 1 pairs, so a block's index is never read past
-    if (maxSegments < 1 || (long long)nblocks * maxSegments > 0x7FFFFFFFll ||
-        ((uintptr_t)d_index & 15u) || index_stride % 16u ||
-        index_stride < 16u + 8u * ((size_t)maxSegments + 1u)) {
-        snprintf(g_err, sizeof g_err, "decompress_safe_indexed: maxSegments %d x %d blocks, index "
-                 "at %p with stride %zu (need 16-byte alignment, a stride that is a multiple of "
-                 "16 and >= 16 + 8 (maxSegments + 1), and fewer than 2^31 segments in all)",
-                 maxSegments, nblocks, d_index, index_stride);
-        return APE_LZ4_GPU_EINVAL;
-    }
-    int rc = check_device();
-    if (rc) return rc;
+    const char *who = "decompress_safe_indexed_batch_dev";
+    if (int rc = check_arrays(who, nblocks, {d_src, d_compressedSize, d_dst,
+                                             d_maxDecompressedSize, d_index, d_result}))
+        return rc;
+    // one wave per (block, segment) in a one-dimensional grid
+    if (!index_ok(d_index, index_stride, maxSegments) ||
+        (long long)nblocks * maxSegments > 0x7FFFFFFFll)
+        return einval("%s: maxSegments %d x %d blocks, index at %p with stride %zu (need 16-byte "
+                      "alignment, a stride that is a multiple of 16 and >= 16 + 8 (maxSegments + "
+                      "1), and fewer than 2^31 segments in all)", who, maxSegments, nblocks,
+                      d_index, index_stride);
+    if (int rc = check_device()) return rc;
     IndexedArgs a{};
     a.src = d_src;
     a.src_size = d_compressedSize;
@@ -826,28 +1006,21 @@ int APE_LZ4_decompress_range_indexed_batch_dev(const char *const *d_src,
                                                const int *d_rangeLen, char *const *d_dst,
                                                const int *d_dstCap, int *d_window, int *d_result,
                                                int nreq, int wavesPerRequest, void *stream) {
-    if (nblocks < 0 || nreq < 0 || (!d_blockOf && nreq != nblocks) ||
-        (nblocks > 0 && (!d_src || !d_compressedSize || !d_index)) ||
-        (nreq > 0 && (!d_rangeStart || !d_rangeLen || !d_dst || !d_dstCap || !d_window ||
-                      !d_result))) {
-        snprintf(g_err, sizeof g_err, "decompress_range_indexed: invalid argument (a null array, "
-                 "a negative count, or no d_blockOf with nreq %d != nblocks %d)", nreq, nblocks);
-        return APE_LZ4_GPU_EINVAL;
-    }
-    // nreq x wavesPerRequest waves in a one-dimensional grid; the stride holds the header and
-    // maxSegments + 1 pairs, so a block's index is never read past
+    const char *who = "decompress_range_indexed_batch_dev";
+    if ((!d_blockOf && nreq != nblocks) ||
+        bad_arrays(nblocks, {d_src, d_compressedSize, d_index}) ||
+        bad_arrays(nreq, {d_rangeStart, d_rangeLen, d_dst, d_dstCap, d_window, d_result}))
+        return einval("%s: invalid argument (a null array, a negative count, or no d_blockOf "
+                      "with nreq %d != nblocks %d)", who, nreq, nblocks);
+    // nreq x wavesPerRequest waves in a one-dimensional grid
     if (wavesPerRequest < 1 || (long long)nreq * wavesPerRequest > 0x7FFFFFFFll ||
-        maxSegments < 1 || ((uintptr_t)d_index & 15u) || index_stride % 16u ||
-        index_stride < 16u + 8u * ((size_t)maxSegments + 1u)) {
-        snprintf(g_err, sizeof g_err, "decompress_range_indexed: %d requests x %d waves, "
-                 "maxSegments %d, index at %p with stride %zu (need wavesPerRequest >= 1, fewer "
-                 "than 2^31 waves in all, maxSegments >= 1, 16-byte alignment and a stride that "
-                 "is a multiple of 16 and >= 16 + 8 (maxSegments + 1))",
-                 nreq, wavesPerRequest, maxSegments, d_index, index_stride);
-        return APE_LZ4_GPU_EINVAL;
-    }
-    int rc = check_device();
-    if (rc) return rc;
+        !index_ok(d_index, index_stride, maxSegments))
+        return einval("%s: %d requests x %d waves, maxSegments %d, index at %p with stride %zu "
+                      "(need wavesPerRequest >= 1, fewer than 2^31 waves in all, maxSegments >= 1, "
+                      "16-byte alignment and a stride that is a multiple of 16 and >= 16 + 8 "
+                      "(maxSegments + 1))", who, nreq, wavesPerRequest, maxSegments, d_index,
+                      index_stride);
+    if (int rc = check_device()) return rc;
     RangeArgs a{};
     a.src = d_src;
     a.src_size = d_compressedSize;
@@ -868,223 +1041,7 @@ int APE_LZ4_decompress_range_indexed_batch_dev(const char *const *d_src,
                          "lz4_range_plan_kernel + lz4_decode_range_kernel");
 }
 
-int APE_LZ4_compress_large_batch_dev(const char *const *d_src, const int *d_srcSize,
-                                     char *const *d_dst, const int *d_dstCap, int *d_result,
-                                     int nblocks, int maxSrcSize, int acceleration,
-                                     void *d_scratch, size_t scratch_bytes, void *stream) {
-    return large_batch(d_src, d_srcSize, d_dst, d_dstCap, d_result, nblocks, maxSrcSize,
-                       acceleration, d_scratch, scratch_bytes, stream, nullptr);
-}
-
-int APE_LZ4_compress_large_timed_dev(const char *const *d_src, const int *d_srcSize,
-                                     char *const *d_dst, const int *d_dstCap, int *d_result,
-                                     int nblocks, int maxSrcSize, int acceleration,
-                                     void *d_scratch, size_t scratch_bytes, void *stream,
-                                     float *ms4) {
-    if (!ms4) return APE_LZ4_GPU_EINVAL;
-    hipEvent_t ev[5] = {};
-    hipError_t e = hipSuccess;
-    for (int q = 0; q < 5 && e == hipSuccess; q++) e = hipEventCreate(&ev[q]);
-    int rc = e == hipSuccess ? APE_LZ4_GPU_OK : finish_launch(e, "hipEventCreate");
-    if (rc == APE_LZ4_GPU_OK)
-        rc = large_batch(d_src, d_srcSize, d_dst, d_dstCap, d_result, nblocks, maxSrcSize,
-                         acceleration, d_scratch, scratch_bytes, stream, ev);
-    for (int q = 0; q < 4; q++) ms4[q] = 0.f;
-    if (rc == APE_LZ4_GPU_OK && nblocks > 0) {
-        e = hipEventSynchronize(ev[4]);
-        for (int q = 0; q < 4 && e == hipSuccess; q++) e = hipEventElapsedTime(&ms4[q], ev[q], ev[q + 1]);
-        rc = finish_launch(e, "compress_large stage events");
-    }
-    for (int q = 0; q < 5; q++)
-        if (ev[q]) (void)hipEventDestroy(ev[q]);
-    return rc;
-}
-
-namespace {
-int large_batch(const char *const *d_src, const int *d_srcSize, char *const *d_dst,
-                const int *d_dstCap, int *d_result, int nblocks, int maxSrcSize, int acceleration,
-                void *d_scratch, size_t scratch_bytes, void *stream, hipEvent_t *ev,
-                int restartBytes, void *d_index, size_t index_stride) {
-    if (nblocks < 0 || (nblocks > 0 && (!d_src || !d_srcSize || !d_dst || !d_dstCap ||
-                                         !d_result || !d_scratch))) {
-        snprintf(g_err, sizeof g_err, "invalid argument");
-        return APE_LZ4_GPU_EINVAL;
-    }
-    if (maxSrcSize < 1 || maxSrcSize > kLargeMaxSrc) {
-        snprintf(g_err, sizeof g_err, "compress_large: maxSrcSize %d outside [1, %d]", maxSrcSize,
-                 kLargeMaxSrc);
-        return APE_LZ4_GPU_EINVAL;
-    }
-    if (!restart_ok(restartBytes)) {
-        snprintf(g_err, sizeof g_err, "compress_large: restartBytes %d is neither 0 nor a positive "
-                 "multiple of the slice size %d", restartBytes, large_slice_size());
-        return APE_LZ4_GPU_EINVAL;
-    }
-    if (d_index && (((uintptr_t)d_index & 15u) || index_stride % 16u ||
-                    index_stride < large_index_size(maxSrcSize, restartBytes))) {
-        snprintf(g_err, sizeof g_err, "compress_large: index at %p with stride %zu, need 16-byte "
-                 "alignment and a stride that is a multiple of 16 and >= %zu", d_index,
-                 index_stride, large_index_size(maxSrcSize, restartBytes));
-        return APE_LZ4_GPU_EINVAL;
-    }
-    int rc = check_device();
-    if (rc) return rc;
-    if (nblocks == 0) return APE_LZ4_GPU_OK;
-    LargeArgs a{};
-    a.restart = restartBytes;
-    a.index = (char *)d_index;
-    a.index_stride = index_stride;
-    a.src = d_src;
-    a.src_size = d_srcSize;
-    a.dst = d_dst;
-    a.dst_cap = d_dstCap;
-    a.result = d_result;
-    a.nblocks = nblocks;
-    a.max_src = maxSrcSize;
-    a.buf = (char *)d_scratch;
-    const size_t need = large_scratch_layout(nblocks, maxSrcSize, &a);
-    if (need == 0) {
-        snprintf(g_err, sizeof g_err, "compress_large: %d inputs of up to %d bytes are more slices "
-                 "than one call takes; split the batch", nblocks, maxSrcSize);
-        return APE_LZ4_GPU_EINVAL;
-    }
-    if (scratch_bytes < need || ((uintptr_t)d_scratch & 15u)) {
-        snprintf(g_err, sizeof g_err, "compress_large: scratch of %zu bytes at %p, need %zu bytes "
-                 "16-byte aligned", scratch_bytes, d_scratch, need);
-        return APE_LZ4_GPU_EINVAL;
-    }
-    return finish_launch(launch_large(a, acceleration, (hipStream_t)stream, ev),
-                         "large plan + lz4_encode_kernel + offsets + stitch");
-}
-}  // namespace
-
 // ---- the high-ratio mode on inputs of any size (lz4_large.hip launch_large_hc) ----
-// Scratch: the large path's layout, then the chain and match tables of one pass of slices.
-namespace {
-size_t up16z(size_t x) { return (x + 15) & ~(size_t)15; }
-
-// slices per pass out of `want` (0 = all): 1 .. min(slots, kHcSub)
-int large_hc_pass(long long nslots, long long want) {
-    long long most = nslots < kHcSub ? nslots : kHcSub;
-    if (most < 1) most = 1;
-    if (want <= 0 || want > most) want = most;
-    return (int)want;
-}
-
-int large_hc_batch(bool opt, const char *const *d_src, const int *d_srcSize, char *const *d_dst,
-                   const int *d_dstCap, int *d_result, int nblocks, int maxSrcSize, int depth,
-                   void *d_scratch, size_t scratch_bytes, int restartBytes, void *d_index,
-                   size_t index_stride, void *stream, float *ms6) {
-    const char *name = opt ? "compress_large_hc_opt" : "compress_large_hc";
-    const size_t slot = opt ? kHcOptSlotBytes : kHcSlotBytes;
-    if (nblocks < 0 || (nblocks > 0 && (!d_src || !d_srcSize || !d_dst || !d_dstCap ||
-                                         !d_result || !d_scratch))) {
-        snprintf(g_err, sizeof g_err, "%s: invalid argument (a null array or a "
-                 "negative count)", name);
-        return APE_LZ4_GPU_EINVAL;
-    }
-    if (depth < 0 || depth > kHcMaxDepth) {
-        snprintf(g_err, sizeof g_err, "%s: depth %d outside 0..%d", name, depth,
-                 kHcMaxDepth);
-        return APE_LZ4_GPU_EINVAL;
-    }
-    if (maxSrcSize < 1 || maxSrcSize > kLargeMaxSrc) {
-        snprintf(g_err, sizeof g_err, "%s: maxSrcSize %d outside [1, %d]", name,
-                 maxSrcSize, kLargeMaxSrc);
-        return APE_LZ4_GPU_EINVAL;
-    }
-    if (!restart_ok(restartBytes)) {
-        snprintf(g_err, sizeof g_err, "%s: restartBytes %d is neither 0 nor a "
-                 "positive multiple of the slice size %d", name, restartBytes,
-                 large_slice_size());
-        return APE_LZ4_GPU_EINVAL;
-    }
-    if (d_index && (((uintptr_t)d_index & 15u) || index_stride % 16u ||
-                    index_stride < large_index_size(maxSrcSize, restartBytes))) {
-        snprintf(g_err, sizeof g_err, "%s: index at %p with stride %zu, need "
-                 "16-byte alignment and a stride that is a multiple of 16 and >= %zu", name,
-                 d_index, index_stride, large_index_size(maxSrcSize, restartBytes));
-        return APE_LZ4_GPU_EINVAL;
-    }
-    size_t base = 0;
-    LargeArgs a{};
-    if (nblocks > 0) {
-        a.restart = restartBytes;
-        a.index = (char *)d_index;
-        a.index_stride = index_stride;
-        a.src = d_src;
-        a.src_size = d_srcSize;
-        a.dst = d_dst;
-        a.dst_cap = d_dstCap;
-        a.result = d_result;
-        a.nblocks = nblocks;
-        a.max_src = maxSrcSize;
-        a.buf = (char *)d_scratch;
-        base = up16z(large_scratch_layout(nblocks, maxSrcSize, &a));
-        if (base == 0) {
-            snprintf(g_err, sizeof g_err, "%s: %d inputs of up to %d bytes are "
-                     "more slices than one call takes; split the batch", name, nblocks,
-                     maxSrcSize);
-            return APE_LZ4_GPU_EINVAL;
-        }
-        if (scratch_bytes < base + slot || ((uintptr_t)d_scratch & 15u)) {
-            snprintf(g_err, sizeof g_err, "%s: scratch of %zu bytes at %p, need "
-                     "%zu bytes 16-byte aligned", name, scratch_bytes, d_scratch, base + slot);
-            return APE_LZ4_GPU_EINVAL;
-        }
-    }
-    int rc = check_device();
-    if (rc) return rc;
-    if (nblocks == 0) return APE_LZ4_GPU_OK;
-    // as many slices per pass as the caller's scratch holds
-    const int pass = large_hc_pass(a.nslots, (long long)((scratch_bytes - base) / slot));
-    const char *what = "large plan + lz4_hc kernels + offsets + stitch";
-    const hipStream_t s = (hipStream_t)stream;
-    const int d = depth ? depth : kHcDefaultDepth;
-    if (!ms6)
-        return finish_launch(launch_large_hc(a, d, (char *)d_scratch + base, pass, s, nullptr, opt),
-                             what);
-    // the timed form: events around every launch, the passes' times summed per kernel
-    const int passes = large_hc_passes(a.nslots, pass), nev = 5 + 3 * passes;
-    std::vector<hipEvent_t> ev((size_t)nev, nullptr);
-    hipError_t e = hipSuccess;
-    for (int q = 0; q < nev && e == hipSuccess; q++) e = hipEventCreate(&ev[q]);
-    rc = e == hipSuccess ? APE_LZ4_GPU_OK : finish_launch(e, "hipEventCreate");
-    if (rc == APE_LZ4_GPU_OK)
-        rc = finish_launch(launch_large_hc(a, d, (char *)d_scratch + base, pass, s, ev.data(), opt),
-                           what);
-    for (int q = 0; q < 6; q++) ms6[q] = 0.f;
-    if (rc == APE_LZ4_GPU_OK) {
-        e = hipEventSynchronize(ev[nev - 1]);
-        auto span = [&](int slot, int from) {
-            float ms = 0.f;
-            if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[from], ev[from + 1]);
-            ms6[slot] += ms;
-        };
-        span(0, 0);
-        for (int p = 0; p < passes; p++)
-            for (int k = 0; k < 3; k++) span(1 + k, 1 + 3 * p + k);
-        span(4, 1 + 3 * passes);
-        span(5, 2 + 3 * passes);   // (the index launch, after it, is not in any figure)
-        rc = finish_launch(e, "compress_large_hc stage events");
-    }
-    for (int q = 0; q < nev; q++)
-        if (ev[q]) (void)hipEventDestroy(ev[q]);
-    return rc;
-}
-}  // namespace
-
-namespace {
-size_t large_hc_scratch(int nblocks, int maxSrcSize, int passSlices, size_t slot) {
-    if (nblocks < 0 || maxSrcSize < 1 || maxSrcSize > kLargeMaxSrc || passSlices < 0) return 0;
-    const size_t base = large_scratch_layout(nblocks, maxSrcSize, nullptr);
-    if (!base) return (size_t)-1;   // more slice slots than one call takes: split the batch
-    const long long S = large_slice_size();
-    const long long nsl = maxSrcSize <= kMaxBlock ? 1 : ((long long)maxSrcSize + S - 1) / S;
-    return up16z(base) + (size_t)large_hc_pass(nblocks * nsl, passSlices) * slot;
-}
-}  // namespace
-
 size_t APE_LZ4_compress_large_hc_scratch_size(int nblocks, int maxSrcSize, int passSlices) {
     return large_hc_scratch(nblocks, maxSrcSize, passSlices, kHcSlotBytes);
 }
@@ -1099,9 +1056,10 @@ int APE_LZ4_compress_large_hc_opt_batch_dev(const char *const *d_src, const int 
                                             void *d_scratch, size_t scratch_bytes,
                                             int restartBytes, void *d_index, size_t index_stride,
                                             void *stream) {
-    return large_hc_batch(true, d_src, d_srcSize, d_dst, d_dstCap, d_result, nblocks, maxSrcSize,
-                          depth, d_scratch, scratch_bytes, restartBytes, d_index, index_stride,
-                          stream, nullptr);
+    return large_hc_batch("compress_large_hc_opt_batch_dev", true,
+                          large_in(d_src, d_srcSize, d_dst, d_dstCap, d_result, nblocks,
+                                   maxSrcSize, d_scratch, restartBytes, d_index, index_stride),
+                          depth, scratch_bytes, stream, nullptr);
 }
 
 int APE_LZ4_compress_large_hc_batch_dev(const char *const *d_src, const int *d_srcSize,
@@ -1109,9 +1067,10 @@ int APE_LZ4_compress_large_hc_batch_dev(const char *const *d_src, const int *d_s
                                         int nblocks, int maxSrcSize, int depth, void *d_scratch,
                                         size_t scratch_bytes, int restartBytes, void *d_index,
                                         size_t index_stride, void *stream) {
-    return large_hc_batch(false, d_src, d_srcSize, d_dst, d_dstCap, d_result, nblocks, maxSrcSize,
-                          depth, d_scratch, scratch_bytes, restartBytes, d_index, index_stride,
-                          stream, nullptr);
+    return large_hc_batch("compress_large_hc_batch_dev", false,
+                          large_in(d_src, d_srcSize, d_dst, d_dstCap, d_result, nblocks,
+                                   maxSrcSize, d_scratch, restartBytes, d_index, index_stride),
+                          depth, scratch_bytes, stream, nullptr);
 }
 
 int APE_LZ4_compress_large_hc_timed_dev(const char *const *d_src, const int *d_srcSize,
@@ -1119,28 +1078,20 @@ int APE_LZ4_compress_large_hc_timed_dev(const char *const *d_src, const int *d_s
                                         int nblocks, int maxSrcSize, int depth, void *d_scratch,
                                         size_t scratch_bytes, int restartBytes, void *stream,
                                         float *ms6) {
-    if (!ms6) return APE_LZ4_GPU_EINVAL;
-    return large_hc_batch(false, d_src, d_srcSize, d_dst, d_dstCap, d_result, nblocks, maxSrcSize,
-                          depth, d_scratch, scratch_bytes, restartBytes, nullptr, 0, stream, ms6);
+    if (!ms6) return einval("compress_large_hc_timed_dev: ms6 is null");
+    return large_hc_batch("compress_large_hc_timed_dev", false,
+                          large_in(d_src, d_srcSize, d_dst, d_dstCap, d_result, nblocks,
+                                   maxSrcSize, d_scratch, restartBytes),
+                          depth, scratch_bytes, stream, ms6);
 }
 
+// ---- the strided form, and the framed stream of independent blocks (lz4_frame.hip) ----
 int APE_LZ4_compress_batch_strided_dev(const char *d_src, size_t src_stride, const int *d_srcSize,
                                        char *d_dst, size_t dst_stride, const int *d_dstCap,
                                        int *d_result, int nblocks, void *stream) {
-    if (nblocks < 0 || (nblocks > 0 && (!d_src || !d_srcSize || !d_dst || !d_result)))
-        return APE_LZ4_GPU_EINVAL;
-    if (!d_dstCap && dst_stride > 0x7FFFFFFF) return APE_LZ4_GPU_EINVAL;
-    int rc = check_device();
-    if (rc) return rc;
-    BlockArgs a{};
-    a.src_base = d_src;
-    a.dst_base = d_dst;
-    a.src_stride = src_stride;
-    a.dst_stride = dst_stride;
-    a.src_size = d_srcSize;
-    a.dst_cap = d_dstCap;
-    a.result = d_result;
-    a.nblocks = nblocks;
+    BlockArgs a = strided_args(d_src, src_stride, d_srcSize, d_dst, dst_stride, d_dstCap,
+                               d_result, nblocks);
+    if (int rc = ready_strided("compress_batch_strided_dev", a)) return rc;
     return finish_launch(launch_encode(a, (hipStream_t)stream), "lz4_encode_kernel");
 }
 
@@ -1148,33 +1099,23 @@ int APE_LZ4_decompress_safe_batch_strided_dev(const char *d_src, size_t src_stri
                                               const int *d_compressedSize, char *d_dst,
                                               size_t dst_stride, const int *d_maxDecompressedSize,
                                               int *d_result, int nblocks, void *stream) {
-    if (nblocks < 0 || (nblocks > 0 && (!d_src || !d_compressedSize || !d_dst || !d_result)))
-        return APE_LZ4_GPU_EINVAL;
-    if (!d_maxDecompressedSize && dst_stride > 0x7FFFFFFF) return APE_LZ4_GPU_EINVAL;
-    int rc = check_device();
-    if (rc) return rc;
-    BlockArgs a{};
-    a.src_base = d_src;
-    a.dst_base = d_dst;
-    a.src_stride = src_stride;
-    a.dst_stride = dst_stride;
-    a.src_size = d_compressedSize;
-    a.dst_cap = d_maxDecompressedSize;
-    a.result = d_result;
-    a.nblocks = nblocks;
+    BlockArgs a = strided_args(d_src, src_stride, d_compressedSize, d_dst, dst_stride,
+                               d_maxDecompressedSize, d_result, nblocks);
+    if (int rc = ready_strided("decompress_safe_batch_strided_dev", a)) return rc;
     return finish_launch(launch_decode(a, false, (hipStream_t)stream), "lz4_decode_kernel");
 }
 
-// ---- framed stream of independent blocks (lz4_frame.hip) ----
 size_t APE_LZ4_frame_scratch_size(int nblocks) {
     return nblocks < 0 ? 0 : (size_t)frame_scratch_elems(nblocks) * sizeof(long long);
 }
 
+// (the offsets have nblocks + 1 entries: the arrays are needed for an empty batch too)
 int APE_LZ4_frame_offsets_dev(const int *d_compressedSize, long long *d_off,
                               void *d_scratch, int nblocks, void *stream) {
-    if (nblocks < 0 || !d_compressedSize || !d_off || !d_scratch) return APE_LZ4_GPU_EINVAL;
-    int rc = check_device();
-    if (rc) return rc;
+    if (nblocks < 0 || !d_compressedSize || !d_off || !d_scratch)
+        return einval("frame_offsets_dev: invalid argument (a null array or a negative count, "
+                      "nblocks %d)", nblocks);
+    if (int rc = check_device()) return rc;
     return finish_launch(launch_frame_offsets(d_compressedSize, d_off, (long long *)d_scratch,
                                               nblocks, (hipStream_t)stream),
                          "frame offsets");
@@ -1183,10 +1124,10 @@ int APE_LZ4_frame_offsets_dev(const int *d_compressedSize, long long *d_off,
 int APE_LZ4_frame_pack_strided_dev(const char *d_comp, size_t comp_stride,
                                    const int *d_compressedSize, const long long *d_off,
                                    char *d_frames, int nblocks, void *stream) {
-    if (nblocks < 0 || (nblocks > 0 && (!d_comp || !d_compressedSize || !d_off || !d_frames)))
-        return APE_LZ4_GPU_EINVAL;
-    int rc = check_device();
-    if (rc) return rc;
+    if (int rc = check_arrays("frame_pack_strided_dev", nblocks,
+                              {d_comp, d_compressedSize, d_off, d_frames}))
+        return rc;
+    if (int rc = check_device()) return rc;
     return finish_launch(launch_frame_pack(d_comp, comp_stride, d_compressedSize, d_off,
                                            d_frames, nblocks, (hipStream_t)stream),
                          "frame pack");
@@ -1196,42 +1137,34 @@ int APE_LZ4_decompress_safe_frames_dev(const char *d_frames, const long long *d_
                                        char *d_dst, size_t dst_stride,
                                        const int *d_maxDecompressedSize, int *d_result,
                                        int nblocks, void *stream) {
-    if (nblocks < 0 || (nblocks > 0 && (!d_frames || !d_off || !d_dst || !d_result)))
-        return APE_LZ4_GPU_EINVAL;
-    if (!d_maxDecompressedSize && dst_stride > 0x7FFFFFFF) return APE_LZ4_GPU_EINVAL;
-    int rc = check_device();
-    if (rc) return rc;
-    BlockArgs a{};
-    a.src_base = d_frames;
+    BlockArgs a = strided_args(d_frames, 0, nullptr, d_dst, dst_stride, d_maxDecompressedSize,
+                               d_result, nblocks);
     a.frame_off = d_off;
-    a.dst_base = d_dst;
-    a.dst_stride = dst_stride;
-    a.dst_cap = d_maxDecompressedSize;
-    a.result = d_result;
-    a.nblocks = nblocks;
+    if (int rc = ready_strided("decompress_safe_frames_dev", a)) return rc;
     return finish_launch(launch_decode(a, false, (hipStream_t)stream), "lz4_decode_kernel");
 }
 
 int APE_LZ4_compress_batch_host(const char *const *h_src, const int *h_srcSize,
                                 char *const *h_dst, const int *h_dstCap, int *h_result,
                                 int nblocks) {
-    return host_batch(0, 1, h_src, h_srcSize, h_dst, h_dstCap, nullptr, h_result, nblocks);
+    return host_batch("compress_batch_host", 0, 1, h_src, h_srcSize, h_dst, h_dstCap, nullptr,
+                      h_result, nblocks);
 }
 
 int APE_LZ4_decompress_safe_batch_host(const char *const *h_src, const int *h_compressedSize,
                                        char *const *h_dst, const int *h_maxDecompressedSize,
                                        int *h_result, int nblocks) {
-    return host_batch(1, 1, h_src, h_compressedSize, h_dst, h_maxDecompressedSize, nullptr,
-                      h_result, nblocks);
+    return host_batch("decompress_safe_batch_host", 1, 1, h_src, h_compressedSize, h_dst,
+                      h_maxDecompressedSize, nullptr, h_result, nblocks);
 }
 
 int APE_LZ4_synth_blocks_dev(char *d_out, size_t stride, int blockSize, long long first_block,
                              int nblocks, int kind, void *stream) {
     if (nblocks < 0 || blockSize < 0 || blockSize > kMaxBlock || (nblocks > 0 && !d_out) ||
         stride < (size_t)blockSize)
-        return APE_LZ4_GPU_EINVAL;
-    int rc = check_device();
-    if (rc) return rc;
+        return einval("synth_blocks_dev: nblocks %d of %d bytes (0..%d) at %p with stride %zu",
+                      nblocks, blockSize, kMaxBlock, d_out, stride);
+    if (int rc = check_device()) return rc;
     return finish_launch(launch_synth(d_out, stride, blockSize, first_block, nblocks, kind,
                                       (hipStream_t)stream),
                          "lz4_synth_kernel");
@@ -1254,15 +1187,15 @@ int APE_LZ4_debug_stats(int which, unsigned long long *out16, int reset) {
 // ---- internal shim for the one-shot C API (ape_lz4_api.c) ----
 int ape_lz4_gpu_compress_one(const char *src, char *dst, int n, int cap, int accel, int *rt) {
     int res = 0;
-    *rt = host_batch(0, accel, &src, &n, &dst, &cap, nullptr, &res, 1);
+    *rt = host_batch("compress_one", 0, accel, &src, &n, &dst, &cap, nullptr, &res, 1);
     return res;
 }
 
 int ape_lz4_gpu_decompress_one(const char *src, char *dst, int csize, int cap, int partial,
                                int target, int *rt) {
     int res = 0;
-    *rt = host_batch(partial ? 2 : 1, 1, &src, &csize, &dst, &cap, partial ? &target : nullptr,
-                     &res, 1);
+    *rt = host_batch("decompress_one", partial ? 2 : 1, 1, &src, &csize, &dst, &cap,
+                     partial ? &target : nullptr, &res, 1);
     return res;
 }
 
