@@ -374,6 +374,13 @@ int APE_LZ4_compress_hc_opt_usingCDict_batch_dev(const char *const *d_src, const
                                                  int maxSrcSize, int depth, void *d_scratch,
                                                  size_t scratch_bytes, void *stream);
 
+/* ---- dictionary training (lz4_dict_train.hip) ----
+ * The step before cdict_prepare / hc_cdict_prepare: APE_LZ4_dict_train_scratch_size and
+ * APE_LZ4_dict_train_dev build a dictionary from a batch of device-resident sample messages.
+ * They are a family of their own -- they compress and decompress nothing -- and are declared,
+ * with the rule and the reading and writing bounds, in ape_lz4_dict_train.h, which the end of
+ * this header includes. */
+
 /* ---- inputs larger than one encoder block, as ONE LZ4 block (lz4_large.hip) ----
  * == N x APE_LZ4_compress_fast on inputs of any size up to maxSrcSize: d_result[i] <-
  * size of ONE valid LZ4 block of d_src[i][0, d_srcSize[i]) (decodes with decompress_safe,
@@ -760,3 +767,5 @@ int APE_LZ4_synth_blocks_dev(char *d_out, size_t stride, int blockSize,
 #if defined(__cplusplus)
 }
 #endif
+
+#include "ape_lz4_dict_train.h"

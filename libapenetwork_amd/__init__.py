@@ -33,6 +33,7 @@ __all__ = [
     "compress_hc_opt_scratch_size", "compress_hc_opt_ptr_batch", "compress_hc_opt_prefix_ptr_batch",
     "compress_large_hc_opt_scratch_size", "compress_large_hc_opt_ptr_batch",
     "compress_hc_opt_cdict_scratch_size", "compress_hc_opt_cdict_batch",
+    "dict_train_scratch_size", "dict_train",
     "ONESHOT_HOST_ALL",
 ]
 
@@ -120,6 +121,8 @@ def lib():
             "APE_LZ4_compress_hc_usingCDict_batch_dev": (i, [p, p, p, p, p, i, p, i, i, p, sz, p]),
             "APE_LZ4_compress_hc_opt_usingCDict_scratch_size": (sz, [i, i]),
             "APE_LZ4_compress_hc_opt_usingCDict_batch_dev": (i, [p, p, p, p, p, i, p, i, i, p, sz, p]),
+            "APE_LZ4_dict_train_scratch_size": (sz, [i, i, i]),
+            "APE_LZ4_dict_train_dev": (i, [p, p, i, i, p, i, i, p, sz, p, p]),
             "APE_LZ4_compress_large_hc_scratch_size": (sz, [i, i, i]),
             "APE_LZ4_compress_large_hc_batch_dev": (i, [p, p, p, p, p, i, i, i, p, sz, i, p, sz, p]),
             "APE_LZ4_compress_large_hc_timed_dev": (i, [p, p, p, p, p, i, i, i, p, sz, i, p, p]),
@@ -744,6 +747,36 @@ def compress_hc_opt_cdict_batch(src_ptrs, src_sizes, dst_ptrs, caps, results, cd
     _cdict_batch("APE_LZ4_compress_hc_opt_usingCDict_batch_dev", "compress_hc_opt_cdict_batch",
                  hc_cdict_size, src_ptrs, src_sizes, dst_ptrs, caps, results, cdict, stream,
                  max_src_size, depth, scratch)
+
+
+def dict_train_scratch_size(nsamples, max_sample_size, segment_size):
+    """APE_LZ4_dict_train_scratch_size: scratch bytes of one dict_train call (0 for arguments
+    out of range)."""
+    return lib().APE_LZ4_dict_train_scratch_size(nsamples, max_sample_size, segment_size)
+
+
+def dict_train(sample_ptrs, sample_sizes, max_sample_size, dict_tensor, segment_size, scratch,
+               info, stream=None):
+    """APE_LZ4_dict_train_dev: a dictionary of dict_tensor.numel() bytes (uint8 CUDA tensor, any
+    placement; every byte is written) trained on the samples at sample_ptrs (int64 CUDA tensor
+    of pointers) of sample_sizes bytes each (int32; samples above max_sample_size are ignored),
+    by the rule of tests/dicttrainmodel.py with segments of segment_size bytes.  scratch: uint8
+    CUDA tensor of at least dict_train_scratch_size(N, max_sample_size, segment_size) bytes,
+    16-byte aligned; info: int32 CUDA tensor of 4, which gets {bytes used, picks, samples
+    ignored, 0}.  Allocates nothing, so it can be graph-captured; dict_tensor can go straight
+    into cdict_prepare or hc_cdict_prepare on the same stream.  Returns dict_tensor."""
+    import torch
+    what = "dict_train"
+    n = _count(what, "sample_sizes", sample_sizes)
+    _ptr_args(what, n, sample_ptrs=sample_ptrs, sample_sizes=sample_sizes)
+    _bytes(dict_tensor, what + " dict")
+    _bytes(scratch, what + " scratch")
+    _arr(info, what + " info", torch.int32, 4)
+    _call("APE_LZ4_dict_train_dev", _ptr(sample_ptrs) if n else None,
+          _ptr(sample_sizes) if n else None, n, max_sample_size, _ptr(dict_tensor),
+          dict_tensor.numel(), segment_size, _ptr(scratch), scratch.numel(), _ptr(info),
+          _stream(stream))
+    return dict_tensor
 
 
 def compress_large_hc_scratch_size(nblocks, max_src_size, pass_slices=0):

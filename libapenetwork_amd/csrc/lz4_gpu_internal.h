@@ -329,6 +329,59 @@ struct HcDictOptArgs {
 };
 // chain build, search, price + emit (one wave per message): three launches
 hipError_t launch_encode_hc_cdict_opt(const HcDictOptArgs &o, hipStream_t s);
+// ---- dictionary training (lz4_dict_train.hip) ----
+// tests/dicttrainmodel.py is the definition and restates these constants: 8-byte substrings of
+// the samples are counted in a table of 2^kDtBits u32 entries, and rounds of scored segments
+// ("slots": every segment / 4 bytes of every sample) pick the dictionary's pieces.
+constexpr int kDtSub = 8;                                // d: bytes of a counted substring
+constexpr int kDtBits = 20;                              // F: the table has 2^F entries
+constexpr uint64_t kDtPrime = 0x9E3779B185EBCA87ull;     // index = (u64 LE * prime) >> (64 - F)
+constexpr uint32_t kDtTable = 1u << kDtBits;
+constexpr int kDtMinSeg = 16, kDtMaxSeg = 1024, kDtMaxDict = 65536;
+constexpr int kDtMinSample = kDtSub, kDtMaxSample = 0x7E000000;
+constexpr int kDtMaxGroups = 1024;   // score workgroups of a round, one partial each
+// Scratch: the table, the state, then one partial per score workgroup.
+struct DtState {
+    uint32_t used, picks, ignored, zero;   // bytes and segments picked so far; samples ignored
+};
+struct DtPartial {
+    unsigned long long score;   // a workgroup's best: highest score, then lowest slot
+    uint32_t slot, zero;
+};
+constexpr size_t kDtStateAt = (size_t)kDtTable * sizeof(uint32_t);
+constexpr size_t kDtPartialAt = kDtStateAt + sizeof(DtState);
+static_assert(sizeof(DtState) == 16 && sizeof(DtPartial) == 16, "scratch regions");
+// slots per sample (J), slots in all (M; < 2^31 given nsamples * max_sample < 2^31), and the
+// score workgroups a round of `slots` slots gets (four waves each, one slot per wave and trip)
+inline long long dt_slots_per_sample(int max_sample, int segment) {
+    const int st = segment / 4;
+    return ((long long)max_sample + st - 1) / st;
+}
+inline long long dt_slots(int nsamples, int max_sample, int segment) {
+    return (long long)nsamples * dt_slots_per_sample(max_sample, segment);
+}
+inline int dt_groups(long long slots) {
+    const long long g = (slots + 3) / 4;
+    return g < 1 ? 1 : g > kDtMaxGroups ? kDtMaxGroups : (int)g;
+}
+inline size_t dt_scratch_bytes(int nsamples, int max_sample, int segment) {
+    return kDtPartialAt +
+           (size_t)dt_groups(dt_slots(nsamples, max_sample, segment)) * sizeof(DtPartial);
+}
+struct DtArgs {
+    const char *const *samples;   // caller's arrays, one entry per sample
+    const int *size;
+    int nsamples, max_sample;
+    char *dict;
+    int capacity, segment;
+    uint32_t *freq;               // the scratch's three regions
+    DtState *state;
+    DtPartial *partial;
+    int *info;
+};
+// zero, count, per round with slots: score + pick, finish: 3 + 2 * rounds launches at most
+hipError_t launch_dict_train(const DtArgs &a, hipStream_t s);
+
 // compress_destSize pass 2 (lz4_destsize.hip): scratch slot i (at scratch + i*stride, encoder
 // result sres[i]) -> dst[i] cut to target[i]; src_size[i] <- consumed input
 hipError_t launch_destsize(const char *const *src, int *src_size, char *const *dst,

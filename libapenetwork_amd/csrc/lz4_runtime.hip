@@ -628,6 +628,14 @@ bool index_ok(const void *d_index, size_t index_stride, int maxSegments) {
            index_stride >= 16u + 8u * ((size_t)maxSegments + 1u);
 }
 
+// ---- dictionary training (lz4_dict_train.hip) ----
+// what sizes the slot grid and the scratch; the product bound keeps every u32 count from wrapping
+bool dt_shape_ok(int nsamples, int maxSampleSize, int segmentSize) {
+    return nsamples >= 0 && maxSampleSize >= kDtMinSample && maxSampleSize <= kDtMaxSample &&
+           segmentSize >= kDtMinSeg && segmentSize <= kDtMaxSeg && segmentSize % 16 == 0 &&
+           (long long)nsamples * maxSampleSize <= 0x7FFFFFFFll;
+}
+
 }  // namespace
 
 extern "C" {
@@ -899,6 +907,45 @@ int APE_LZ4_compress_hc_opt_usingCDict_batch_dev(const char *const *d_src, const
     return hc_cdict_batch("compress_hc_opt_usingCDict_batch_dev", true, d_src, d_srcSize, d_dst,
                           d_dstCap, d_result, nblocks, d_cdict, maxSrcSize, depth, d_scratch,
                           scratch_bytes, stream);
+}
+
+// ---- dictionary training (lz4_dict_train.hip) ----
+size_t APE_LZ4_dict_train_scratch_size(int nsamples, int maxSampleSize, int segmentSize) {
+    if (!dt_shape_ok(nsamples, maxSampleSize, segmentSize)) return 0;
+    return dt_scratch_bytes(nsamples, maxSampleSize, segmentSize);
+}
+
+int APE_LZ4_dict_train_dev(const char *const *d_samples, const int *d_sampleSize, int nsamples,
+                           int maxSampleSize, char *d_dict, int dictCapacity, int segmentSize,
+                           void *d_scratch, size_t scratch_bytes, int *d_info, void *stream) {
+    const char *who = "dict_train_dev";
+    if (int rc = check_arrays(who, nsamples, {d_samples, d_sampleSize})) return rc;
+    if (!dt_shape_ok(nsamples, maxSampleSize, segmentSize))
+        return einval("%s: nsamples %d x maxSampleSize %d (%d..%d, product below 2^31), "
+                      "segmentSize %d (a multiple of 16 in %d..%d)", who, nsamples, maxSampleSize,
+                      kDtMinSample, kDtMaxSample, segmentSize, kDtMinSeg, kDtMaxSeg);
+    const size_t need = dt_scratch_bytes(nsamples, maxSampleSize, segmentSize);
+    if (!d_dict || !d_info || dictCapacity < segmentSize || dictCapacity > kDtMaxDict ||
+        !d_scratch || !aligned16(d_scratch) || scratch_bytes < need)
+        return einval("%s: dictionary at %p, dictCapacity %d (%d..%d), info at %p, scratch of %zu "
+                      "bytes at %p (need %zu bytes, 16-byte aligned)", who, (void *)d_dict,
+                      dictCapacity, segmentSize, kDtMaxDict, (void *)d_info, scratch_bytes,
+                      d_scratch, need);
+    if (int rc = check_device()) return rc;
+    DtArgs a{};
+    a.samples = d_samples;
+    a.size = d_sampleSize;
+    a.nsamples = nsamples;
+    a.max_sample = maxSampleSize;
+    a.dict = d_dict;
+    a.capacity = dictCapacity;
+    a.segment = segmentSize;
+    a.freq = (uint32_t *)d_scratch;
+    a.state = (DtState *)((char *)d_scratch + kDtStateAt);
+    a.partial = (DtPartial *)((char *)d_scratch + kDtPartialAt);
+    a.info = d_info;
+    return finish_launch(launch_dict_train(a, (hipStream_t)stream),
+                         "lz4_dict_train zero + count + score + pick + finish kernels");
 }
 
 // ---- inputs of any size as one block (lz4_large.hip) ----
