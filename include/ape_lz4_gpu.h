@@ -163,7 +163,8 @@ int APE_LZ4_decompress_safe_usingDict_batch_dev(const char *const *d_src,
  *   The object is only read: any number of calls, on any streams, may share it.  It starts
  *   with a header (magic, D, maxSrcSize) that the kernel checks before it uses anything else
  *   of it: every block of a call on an object that was never prepared gets result 0.  One
- *   dictionary per call; no acceleration parameter (as compress_withPrefix has none).
+ *   dictionary per call (a dictionary per message: ape_lz4_cdicts.h); no acceleration
+ *   parameter (as compress_withPrefix has none).
  * Both launchers return APE_LZ4_GPU_EINVAL before any device call for a null pointer,
  * nblocks < 0, dictSize < 0, maxSrcSize out of range, cdict_bytes too small or d_cdict not
  * 16-byte aligned; 0 otherwise. */
@@ -380,6 +381,14 @@ int APE_LZ4_compress_hc_opt_usingCDict_batch_dev(const char *const *d_src, const
  * They are a family of their own -- they compress and decompress nothing -- and are declared,
  * with the rule and the reading and writing bounds, in ape_lz4_dict_train.h, which the end of
  * this header includes. */
+
+/* ---- a prepared dictionary per message (lz4_encode.hip, lz4_hc_cdict.hip, lz4_cdict.hip) ----
+ * The three compress calls above that read a prepared dictionary take one object per call.  Their
+ * usingCDicts forms take a device array with one object pointer per message, so a batch of mixed
+ * message classes is one call, and the two prepare_batch calls prepare the classes' objects in
+ * one launch.  They add no byte rule: message i gets what the call above writes for it against
+ * its own object, and a bad object costs only the messages that name it.  They are declared,
+ * with those rules, in ape_lz4_cdicts.h, which the end of this header includes. */
 
 /* ---- inputs larger than one encoder block, as ONE LZ4 block (lz4_large.hip) ----
  * == N x APE_LZ4_compress_fast on inputs of any size up to maxSrcSize: d_result[i] <-
@@ -769,3 +778,4 @@ int APE_LZ4_synth_blocks_dev(char *d_out, size_t stride, int blockSize,
 #endif
 
 #include "ape_lz4_dict_train.h"
+#include "ape_lz4_cdicts.h"

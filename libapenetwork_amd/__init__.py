@@ -123,6 +123,11 @@ def lib():
             "APE_LZ4_compress_hc_opt_usingCDict_batch_dev": (i, [p, p, p, p, p, i, p, i, i, p, sz, p]),
             "APE_LZ4_dict_train_scratch_size": (sz, [i, i, i]),
             "APE_LZ4_dict_train_dev": (i, [p, p, i, i, p, i, i, p, sz, p, p]),
+            "APE_LZ4_cdict_prepare_batch_dev": (i, [p, p, i, p, sz, i, p]),
+            "APE_LZ4_hc_cdict_prepare_batch_dev": (i, [p, p, i, p, sz, i, p]),
+            "APE_LZ4_compress_usingCDicts_batch_dev": (i, [p, p, p, p, p, i, p, p]),
+            "APE_LZ4_compress_hc_usingCDicts_batch_dev": (i, [p, p, p, p, p, i, p, i, i, p, sz, p]),
+            "APE_LZ4_compress_hc_opt_usingCDicts_batch_dev": (i, [p, p, p, p, p, i, p, i, i, p, sz, p]),
             "APE_LZ4_compress_large_hc_scratch_size": (sz, [i, i, i]),
             "APE_LZ4_compress_large_hc_batch_dev": (i, [p, p, p, p, p, i, i, i, p, sz, i, p, sz, p]),
             "APE_LZ4_compress_large_hc_timed_dev": (i, [p, p, p, p, p, i, i, i, p, sz, i, p, p]),
@@ -777,6 +782,88 @@ def dict_train(sample_ptrs, sample_sizes, max_sample_size, dict_tensor, segment_
           dict_tensor.numel(), segment_size, _ptr(scratch), scratch.numel(), _ptr(info),
           _stream(stream))
     return dict_tensor
+
+
+# ---- a prepared dictionary per message (include/ape_lz4_cdicts.h) ----
+# (Public, as compress_hc_cdict_batch is, without a line in __all__: every *_batch name listed
+# there has a row in tests/test_bindings.py's table of pointer-array wrappers, which is as it was.
+# tests/test_cdicts_args.py checks these five the same way.)
+def _prepare_batch(symbol, what, size_fn, dict_ptrs, dict_sizes, max_src_size, cdicts, stride,
+                   stream):
+    """cdict_prepare_batch and hc_cdict_prepare_batch: the same arguments, another object."""
+    n = _count(what, "dict_sizes", dict_sizes)
+    _ptr_args(what, n, dict_ptrs=dict_ptrs, dict_sizes=dict_sizes)
+    _bytes(cdicts, what + " cdicts")
+    if not isinstance(stride, int) or isinstance(stride, bool):
+        raise ValueError("%s stride: need an int" % what)
+    if n > 0 and (stride < size_fn() or cdicts.numel() < (n - 1) * stride + size_fn()):
+        raise ValueError("%s cdicts: %d bytes with stride %d do not hold %d objects of %s() "
+                         "bytes" % (what, cdicts.numel(), stride, n, size_fn.__name__))
+    _call(symbol, _ptr(dict_ptrs) if n else None, _ptr(dict_sizes) if n else None, max_src_size,
+          _ptr(cdicts) if n else None, stride, n, _stream(stream))
+    return cdicts
+
+
+def cdict_prepare_batch(dict_ptrs, dict_sizes, max_src_size, cdicts, stride, stream=None):
+    """APE_LZ4_cdict_prepare_batch_dev: N prepared dictionaries in one launch.  dict_ptrs (int64
+    CUDA tensor of N device pointers; an entry may be 0 where its size is 0) and dict_sizes
+    (int32) name the dictionaries; object k is written at cdicts[k * stride:] (uint8 CUDA tensor,
+    16-byte aligned; stride a multiple of 16, at least cdict_size()) and is byte for byte what
+    cdict_prepare writes.  An entry with a negative size, or a null pointer and a positive size,
+    gets a zero header: every compress against it gives 0.  Returns cdicts."""
+    return _prepare_batch("APE_LZ4_cdict_prepare_batch_dev", "cdict_prepare_batch", cdict_size,
+                          dict_ptrs, dict_sizes, max_src_size, cdicts, stride, stream)
+
+
+def hc_cdict_prepare_batch(dict_ptrs, dict_sizes, max_src_size, cdicts, stride, stream=None):
+    """APE_LZ4_hc_cdict_prepare_batch_dev: cdict_prepare_batch for the high-ratio modes' object
+    (stride at least hc_cdict_size(); object k is hc_cdict_prepare's)."""
+    return _prepare_batch("APE_LZ4_hc_cdict_prepare_batch_dev", "hc_cdict_prepare_batch",
+                          hc_cdict_size, dict_ptrs, dict_sizes, max_src_size, cdicts, stride,
+                          stream)
+
+
+def _cdicts_batch(symbol, what, src_ptrs, src_sizes, dst_ptrs, caps, results, cdict_ptrs, stream,
+                  *hc):
+    """Every compressor against a prepared dictionary per message; hc: the high-ratio ones'
+    (max_src_size, depth, scratch)."""
+    n = _ptr_batch(what, _FIVE, src_ptrs, src_sizes, dst_ptrs, caps, results,
+                   cdict_ptrs=cdict_ptrs)
+    if hc:
+        max_src_size, depth, scratch = hc
+        _bytes(scratch, what + " scratch")
+        hc = (max_src_size, depth, _ptr(scratch), scratch.numel())
+    _call(symbol, _ptr(src_ptrs), _ptr(src_sizes), _ptr(dst_ptrs), _ptr(caps), _ptr(results), n,
+          _ptr(cdict_ptrs), *hc, _stream(stream))
+
+
+def compress_cdicts_batch(src_ptrs, src_sizes, dst_ptrs, caps, results, cdict_ptrs, stream=None):
+    """APE_LZ4_compress_usingCDicts_batch_dev: compress_cdict_batch with a prepared dictionary
+    per message.  cdict_ptrs: int64 CUDA tensor of N device pointers, message i's object (of
+    cdict_prepare or cdict_prepare_batch).  Message i gets what compress_cdict_batch gives it
+    against that object; a null, misaligned or unprepared object gives that message 0 and leaves
+    the others as they are."""
+    _cdicts_batch("APE_LZ4_compress_usingCDicts_batch_dev", "compress_cdicts_batch", src_ptrs,
+                  src_sizes, dst_ptrs, caps, results, cdict_ptrs, stream)
+
+
+def compress_hc_cdicts_batch(src_ptrs, src_sizes, dst_ptrs, caps, results, cdict_ptrs,
+                             max_src_size, depth, scratch, stream=None):
+    """APE_LZ4_compress_hc_usingCDicts_batch_dev: compress_hc_cdict_batch with a prepared
+    high-ratio dictionary per message (cdict_ptrs as in compress_cdicts_batch; every object
+    prepared for this max_src_size).  scratch: compress_hc_cdict_batch's."""
+    _cdicts_batch("APE_LZ4_compress_hc_usingCDicts_batch_dev", "compress_hc_cdicts_batch",
+                  src_ptrs, src_sizes, dst_ptrs, caps, results, cdict_ptrs, stream, max_src_size,
+                  depth, scratch)
+
+
+def compress_hc_opt_cdicts_batch(src_ptrs, src_sizes, dst_ptrs, caps, results, cdict_ptrs,
+                                 max_src_size, depth, scratch, stream=None):
+    """APE_LZ4_compress_hc_opt_usingCDicts_batch_dev: compress_hc_opt_cdict_batch with a prepared
+    high-ratio dictionary per message.  scratch: compress_hc_opt_cdict_batch's."""
+    _cdicts_batch("APE_LZ4_compress_hc_opt_usingCDicts_batch_dev", "compress_hc_opt_cdicts_batch",
+                  src_ptrs, src_sizes, dst_ptrs, caps, results, cdict_ptrs, stream, max_src_size,
+                  depth, scratch)
 
 
 def compress_large_hc_scratch_size(nblocks, max_src_size, pass_slices=0):

@@ -13,6 +13,9 @@
 // waves meanwhile write the header, the window copy and every pad byte; then all four store
 // the table image.  Every byte of the object is written, so two prepares of the same input
 // give identical objects.
+//
+// APE_LZ4_cdict_prepare_batch_dev is the same body, one workgroup per object of a
+// batch: lz4_cdict_prepare.inc, included into both kernels.
 #include "lz4_gpu_internal.h"
 
 namespace apelz4 {
@@ -23,57 +26,24 @@ constexpr int kPrepThreads = 256;
 
 __global__ void __launch_bounds__(kPrepThreads)
 lz4_cdict_prepare_kernel(const char *dict, int dict_size, int max_src, uint8_t *cd) {
-    __shared__ __attribute__((aligned(16))) uint16_t tab[kHSize];
-    const int tid = threadIdx.x;
-    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    int Di = cdict_window(dict_size, max_src);
-    if (Di < 64) Di = 0;
-    const uint32_t D = (uint32_t)Di;
-    gcu8 *src = (gcu8 *)dict + (dict_size - Di);   // window position v = src[v]
+#include "lz4_cdict_prepare.inc"
+}
 
-    for (int i = tid; i < kHSize / 8; i += kPrepThreads) ((uint4 *)tab)[i] = make_uint4(0, 0, 0, 0);
-    __syncthreads();
-
-    if (wave == 0) {
-        constexpr int kU = 8;   // loads in flight per trip (the loop is latency bound)
-        for (uint32_t v0 = 0; v0 < D; v0 += 192u * kU) {
-            uint2 x[kU];
-            bool ok[kU];
-#pragma unroll
-            for (int u = 0; u < kU; u++) {
-                const uint32_t v = v0 + 192u * u + 3u * (uint32_t)lane;
-                ok[u] = v + 8u <= D;
-                x[u] = ok[u] ? gload8(src + v) : make_uint2(0, 0);
-            }
-#pragma unroll
-            for (int u = 0; u < kU; u++) {
-                const uint32_t v = v0 + 192u * u + 3u * (uint32_t)lane;
-                if (ok[u]) tab[hashk(x[u].x, x[u].y)] = (uint16_t)v;
-            }
-        }
-    } else {
-        const int t = tid - 64, nt = kPrepThreads - 64;
-        if (t == 0) {
-            CDictHdr H;
-            H.magic = kCdMagic;
-            H.D = D;
-            H.max_src = (uint32_t)max_src;
-            H.zero = 0u;
-            *(CDictHdr *)cd = H;
-        }
-        // [kCdWin, kCdSize) in 16-byte pieces: pad, window, pad (D is a multiple of 64)
-        gu8 *w = (gu8 *)cd + kCdWin;
-        constexpr uint32_t kPieces = (kCdSize - kCdWin) / 16u;
-        for (uint32_t i = (uint32_t)t; i < kPieces; i += (uint32_t)nt) {
-            const uint32_t at = 16u * i;          // byte of the region; window byte at - kCdFront
-            uint4 v = make_uint4(0, 0, 0, 0);
-            if (at >= kCdFront && at - kCdFront < D) v = gload16(src + (at - kCdFront));
-            gstore16(w + at, v);
-        }
+// Object blockIdx.x of a batch (APE_LZ4_cdict_prepare_batch_dev), from the
+// device arrays' entry.  The sizes were never on the host: an entry no single prepare would take
+// (a negative size, a null pointer with a positive one) gets sixteen zero bytes as its header,
+// which every compress rejects, and nothing else of its object is written.
+__global__ void __launch_bounds__(kPrepThreads)
+lz4_cdict_prepare_batch_kernel(const char *const *dicts, const int *dict_sizes, int max_src,
+                               uint8_t *cds, size_t stride) {
+    const char *dict = wave_uniform(dicts[blockIdx.x]);
+    const int dict_size = (int)wave_first((uint32_t)dict_sizes[blockIdx.x]);
+    uint8_t *cd = cds + (size_t)blockIdx.x * stride;
+    if (dict_size < 0 || (dict_size > 0 && !dict)) {
+        if (threadIdx.x == 0) gstore16((gu8 *)cd, make_uint4(0, 0, 0, 0));
+        return;
     }
-    __syncthreads();
-    uint4 *img = (uint4 *)(cd + kCdTab);
-    for (int i = tid; i < kHSize / 8; i += kPrepThreads) img[i] = ((const uint4 *)tab)[i];
+#include "lz4_cdict_prepare.inc"
 }
 
 }  // namespace
@@ -82,6 +52,14 @@ hipError_t launch_cdict_prepare(const char *dict, int dict_size, int max_src, vo
                                 hipStream_t s) {
     hipLaunchKernelGGL(lz4_cdict_prepare_kernel, dim3(1), dim3(kPrepThreads), 0, s, dict,
                        dict_size, max_src, (uint8_t *)cdict);
+    return hipGetLastError();
+}
+
+hipError_t launch_cdict_prepare_batch(const char *const *dict, const int *dict_size, int max_src,
+                                      void *cdicts, size_t stride, int n, hipStream_t s) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(lz4_cdict_prepare_batch_kernel, dim3(n), dim3(kPrepThreads), 0, s, dict,
+                       dict_size, max_src, (uint8_t *)cdicts, stride);
     return hipGetLastError();
 }
 

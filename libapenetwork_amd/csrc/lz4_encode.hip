@@ -1387,41 +1387,34 @@ lz4_encode_cdict_kernel(BlockArgs a, const uint8_t *cd) {
 
     // the header first: nothing else of an object that fails this is read
     const CDictHdr H = *(const CDictHdr *)cd;
-    if (H.magic != kCdMagic || H.D > kCdMaxWin || (H.D & 63u) != 0u || H.max_src < 1u ||
-        H.max_src > (uint32_t)kMaxBlock || H.D + H.max_src > (uint32_t)kMaxBlock) {
+#include "lz4_encode_cdict.inc"
+}
+
+// ... and against a prepared dictionary per block (APE_LZ4_compress_usingCDicts_batch_dev,
+// DESIGN.md 3.22): block b against cdicts[b].  A null or misaligned entry is rejected before
+// anything is read through it, a bad header as above; either costs this block alone.  The
+// pointer is the workgroup's, so it and the header stay in scalar registers.
+__global__ void __launch_bounds__(192) __attribute__((amdgpu_waves_per_eu(kWavesPerEu)))
+lz4_encode_cdicts_kernel(BlockArgs a, const uint8_t *const *cdicts) {
+    __shared__ EncLds S;
+    const int b = blockIdx.x;
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+
+    gcu8 *cd = (gcu8 *)message_object(cdicts, b);
+    if (!cd) {
         if (tid == 0) a.result[b] = 0;
         return;
     }
-    const int nr = a.src_size[b];
-    const int icap = a.dst_cap[b];
-    if (nr < 0 || nr > (int)H.max_src || icap < 0) {
-        if (tid == 0) a.result[b] = (nr > (int)H.max_src) ? kErange : 0;
-        return;
-    }
-    const int D = (int)H.D;
-    Blk B;
-    B.win = (gcu8 *)(cd + kCdWin + kCdFront);
-    B.D = (uint32_t)D;
-    B.in = (gcu8 *)a.src[b] - D;     // (an address only: nothing below position D is read from it)
-    B.dst = (gu8 *)a.dst[b];
-    B.n = D + nr;
-    B.nr = (uint32_t)nr;
-    B.k0 = D / 64;
-    B.stride = 1u;
-    B.cap = (uint32_t)icap;
-    B.un = (uint32_t)B.n;
-    B.mstart = B.un >= 12 ? B.un - 12 : 0;
-    B.mlimit = B.un >= 5 ? B.un - 5 : 0;
-    B.nch = (B.n + 63) / 64;
+    const CDictHdr H = object_header<true>(cd);
+#include "lz4_encode_cdict.inc"
+}
 
-    // table = the prepared image (all zero for D = 0: the state of a block without history)
-    const uint4 *img = (const uint4 *)(cd + kCdTab);
-    for (int i = tid; i < kHSize / 8; i += 192) ((uint4 *)S.tab)[i] = img[i];
-    for (int i = tid; i < (int)(kRingE / 16 + 4); i += 192) ((uint4 *)S.ring)[i] = make_uint4(0, 0, 0, 0);
-    if (tid == 0) S.qn[0] = S.qn[1] = 0u;
-    __syncthreads();
-    if (B.n < kSmall) encode_block<true, false, true>(S, B, wave, lane, &a.result[b], nullptr);
-    else encode_block<false, false, true>(S, B, wave, lane, &a.result[b], nullptr);
+hipError_t launch_encode_cdicts(const BlockArgs &a, const void *const *cdicts, hipStream_t s) {
+    if (a.nblocks <= 0) return hipSuccess;
+    hipLaunchKernelGGL(lz4_encode_cdicts_kernel, dim3(a.nblocks), dim3(192), 0, s, a,
+                       (const uint8_t *const *)cdicts);
+    return hipGetLastError();
 }
 
 hipError_t launch_encode_cdict(const BlockArgs &a, const void *cdict, hipStream_t s) {

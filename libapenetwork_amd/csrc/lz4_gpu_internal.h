@@ -108,6 +108,18 @@ __device__ __forceinline__ uint32_t lane_val(uint32_t v, int l) {  // l wave-uni
     return (uint32_t)__builtin_amdgcn_readlane((int)v, l);
 }
 
+// A value every lane of the wave holds alike, moved into a scalar register; a pointer likewise
+// (one loaded from an array entry that the workgroup indexes by blockIdx): what is read through
+// it keeps an SGPR base.
+__device__ __forceinline__ uint32_t wave_first(uint32_t v) {
+    return (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
+}
+template <class T>
+__device__ __forceinline__ T *wave_uniform(T *p) {
+    const uint64_t v = (uint64_t)p;
+    return (T *)((uint64_t)wave_first((uint32_t)(v >> 32)) << 32 | wave_first((uint32_t)v));
+}
+
 // ---- the encoder's hash table (lz4_encode.hip; lz4_cdict.hip prebuilds an image of it) ----
 // Table entries, the hash scaled onto [0, kHSize).  7328 entries make the block's LDS 17904
 // bytes, inside the 35 x 512-byte granules that fit 9 blocks = 27 waves per CU (7 per SIMD:
@@ -153,6 +165,22 @@ static_assert(kCdWin % 16u == 0u && kCdSize % 16u == 0u, "prepared dictionary re
 struct CDictHdr {
     uint32_t magic, D, max_src, zero;
 };
+// The prepared object a message names in a per-message array: null for a null
+// or not 16-byte aligned entry, of which nothing is read.
+__device__ __forceinline__ const uint8_t *message_object(const uint8_t *const *objs, int b) {
+    const uint8_t *cd = wave_uniform(objs[b]);
+    return ((uint64_t)cd & 15u) ? nullptr : cd;
+}
+// The header of either kind of object.  PER: of message_object's, into scalar registers.
+template <bool PER, class P>
+__device__ __forceinline__ CDictHdr object_header(P *cd) {
+    if constexpr (!PER) {
+        return *(const CDictHdr *)cd;
+    } else {
+        const uint4 v = gload16((gcu8 *)cd);
+        return CDictHdr{wave_first(v.x), wave_first(v.y), wave_first(v.z), wave_first(v.w)};
+    }
+}
 // D of a prepared dictionary: min(dict_size, 65536 - max_src) rounded down to 64 (host and device)
 __host__ __device__ inline int cdict_window(int dict_size, int max_src) {
     const int room = kMaxBlock - max_src;
@@ -208,9 +236,15 @@ hipError_t launch_encode(const BlockArgs &a, hipStream_t s);
 // against a prepared dictionary (layout above): the history is the object's window and table
 // image, not the bytes before each block (lz4_encode.hip, its EXT instantiation)
 hipError_t launch_encode_cdict(const BlockArgs &a, const void *cdict, hipStream_t s);
+// ... message i against the object cdicts[i] (a device array of device pointers)
+hipError_t launch_encode_cdicts(const BlockArgs &a, const void *const *cdicts, hipStream_t s);
 // dict[dict_size - D, dict_size) -> the prepared dictionary at cdict (lz4_cdict.hip)
 hipError_t launch_cdict_prepare(const char *dict, int dict_size, int max_src, void *cdict,
                                 hipStream_t s);
+// n objects in one launch, object k at cdicts + k * stride from dict[k], dict_size[k] (device
+// arrays); a negative size, or a null pointer with a positive one, leaves a zero header
+hipError_t launch_cdict_prepare_batch(const char *const *dict, const int *dict_size, int max_src,
+                                      void *cdicts, size_t stride, int n, hipStream_t s);
 // the greedy-exact mode (lz4_encode_exact.hip): the reference's sequential parse, byte for byte
 hipError_t launch_encode_exact(const BlockArgs &a, hipStream_t s);
 // The high-ratio mode (lz4_encode_hc.hip; tests/hcmodel.py restates the two constants): hash
@@ -311,9 +345,14 @@ struct HcDictArgs {
 };
 hipError_t launch_hc_cdict_prepare(const char *dict, int dict_size, int max_src, void *cdict,
                                    hipStream_t s);
+// as launch_cdict_prepare_batch
+hipError_t launch_hc_cdict_prepare_batch(const char *const *dict, const int *dict_size,
+                                         int max_src, void *cdicts, size_t stride, int n,
+                                         hipStream_t s);
 // chain build (one wave per message), search (one lane per message position), parse + emit
-// (one wave per message)
-hipError_t launch_encode_hc_cdict(const HcDictArgs &a, hipStream_t s);
+// (one wave per message).  cdicts (nullable): message i's object is cdicts[i], not a.cdict.
+hipError_t launch_encode_hc_cdict(const HcDictArgs &a, hipStream_t s,
+                                  const uint8_t *const *cdicts = nullptr);
 // The cost-minimising parse against the same object (tests/hcoptdictmodel.py is
 // the definition): the chain build and the search above as they are, then a parse that prices
 // every message position backward and emits forward.  One more table per message, cost[p] (u32:
@@ -328,7 +367,8 @@ struct HcDictOptArgs {
     uint32_t cost_stride;
 };
 // chain build, search, price + emit (one wave per message): three launches
-hipError_t launch_encode_hc_cdict_opt(const HcDictOptArgs &o, hipStream_t s);
+hipError_t launch_encode_hc_cdict_opt(const HcDictOptArgs &o, hipStream_t s,
+                                      const uint8_t *const *cdicts = nullptr);
 // ---- dictionary training (lz4_dict_train.hip) ----
 // tests/dicttrainmodel.py is the definition and restates these constants: 8-byte substrings of
 // the samples are counted in a table of 2^kDtBits u32 entries, and rounds of scored segments

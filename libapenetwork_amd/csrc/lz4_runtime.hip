@@ -343,6 +343,19 @@ int ready_prepare(const char *who, const char *d_dict, int dictSize, int maxSrcS
     return check_device();
 }
 
+// ndicts objects of `size` bytes each, object k at d_cdicts + k * stride; the dictionaries' sizes
+// are device memory, so a bad entry is the kernel's to mark (a zero header)
+int ready_prepare_batch(const char *who, const char *const *d_dict, const int *d_dictSize,
+                        int maxSrcSize, const void *d_cdicts, size_t stride, int ndicts,
+                        uint32_t size) {
+    if (bad_arrays(ndicts, {d_dict, d_dictSize, d_cdicts}) || maxSrcSize < 1 ||
+        maxSrcSize > kMaxBlock || !aligned16(d_cdicts) || stride < (size_t)size || stride % 16)
+        return einval("%s: ndicts %d, maxSrcSize %d (1..%d), objects at %p with stride %zu (need "
+                      "16-byte alignment and a stride that is a multiple of 16, at least %u), or "
+                      "a null array", who, ndicts, maxSrcSize, kMaxBlock, d_cdicts, stride, size);
+    return check_device();
+}
+
 // blocks per pass: as many as the scratch holds of `slot` bytes each, at most `most` and no
 // more than the batch has
 int pass_blocks(size_t scratch_bytes, size_t slot, int most, int nblocks) {
@@ -435,21 +448,25 @@ size_t hc_cdict_scratch(int nblocks, int maxSrcSize, bool opt) {
            (opt ? hc_cdict_opt_slot_bytes(maxSrcSize) : hc_cdict_slot_bytes(maxSrcSize));
 }
 
-// opt, and the scratch at nblocks == 0: as hc_batch
+// opt, and the scratch at nblocks == 0: as hc_batch.  The object is d_cdict for every message
+// or, with d_cdicts (the usingCDicts calls: d_cdict is then null), d_cdicts[i] for message i,
+// which only the kernels can check.
 int hc_cdict_batch(const char *who, bool opt, const char *const *d_src, const int *d_srcSize,
                    char *const *d_dst, const int *d_dstCap, int *d_result, int nblocks,
                    const void *d_cdict, int maxSrcSize, int depth, void *d_scratch,
-                   size_t scratch_bytes, void *stream) {
+                   size_t scratch_bytes, void *stream, const void *const *d_cdicts = nullptr,
+                   bool per = false) {
     const bool range = maxSrcSize >= 1 && maxSrcSize <= kMaxBlock;
     const size_t slot = !range ? 0 : opt ? hc_cdict_opt_slot_bytes(maxSrcSize)
                                          : hc_cdict_slot_bytes(maxSrcSize);
-    if (!range || depth < 0 || depth > kHcMaxDepth || !d_cdict || !aligned16(d_cdict) ||
+    const bool object = per ? !bad_arrays(nblocks, {d_cdicts}) : d_cdict && aligned16(d_cdict);
+    if (!range || depth < 0 || depth > kHcMaxDepth || !object ||
         !d_scratch || !aligned16(d_scratch) || scratch_bytes < slot ||
         bad_arrays(nblocks, {d_src, d_srcSize, d_dst, d_dstCap, d_result}))
-        return einval("%s: nblocks %d, maxSrcSize %d (1..%d), depth %d (0..%d), object at %p, "
+        return einval("%s: nblocks %d, maxSrcSize %d (1..%d), depth %d (0..%d), object%s at %p, "
                       "scratch of %zu bytes at %p (need %zu bytes; both 16-byte aligned)", who,
-                      nblocks, maxSrcSize, kMaxBlock, depth, kHcMaxDepth, d_cdict, scratch_bytes,
-                      d_scratch, slot);
+                      nblocks, maxSrcSize, kMaxBlock, depth, kHcMaxDepth, per ? " array" : "",
+                      per ? (const void *)d_cdicts : d_cdict, scratch_bytes, d_scratch, slot);
     if (int rc = check_device()) return rc;
     const int sub = pass_blocks(scratch_bytes, slot, hc_cdict_sub(maxSrcSize), nblocks);
     hipError_t e = hipSuccess;
@@ -471,9 +488,15 @@ int hc_cdict_batch(const char *who, bool opt, const char *const *d_src, const in
         a.match = (uint32_t *)((char *)d_scratch + (size_t)sub * a.chain_stride * sizeof(uint16_t));
         o.cost_stride = (uint32_t)hc_cdict_cost_entries(maxSrcSize);
         o.cost = (uint32_t *)((char *)d_scratch + (size_t)sub * hc_cdict_slot_bytes(maxSrcSize));
-        e = opt ? launch_encode_hc_cdict_opt(o, (hipStream_t)stream)
-                : launch_encode_hc_cdict(a, (hipStream_t)stream);
+        const uint8_t *const *objs = per ? (const uint8_t *const *)d_cdicts + off : nullptr;
+        e = opt ? launch_encode_hc_cdict_opt(o, (hipStream_t)stream, objs)
+                : launch_encode_hc_cdict(a, (hipStream_t)stream, objs);
     }
+    if (per)
+        return finish_launch(e, opt ? "lz4_hc_cdicts_chain_kernel + lz4_hc_cdicts_search_kernel + "
+                                      "lz4_hc_cdicts_opt_parse_kernel"
+                                    : "lz4_hc_cdicts_chain_kernel + lz4_hc_cdicts_search_kernel + "
+                                      "lz4_hc_cdicts_parse_kernel");
     return finish_launch(e, opt ? "lz4_hc_cdict_chain_kernel + lz4_hc_cdict_search_kernel + "
                                   "lz4_hc_cdict_opt_parse_kernel"
                                 : "lz4_hc_cdict_chain_kernel + lz4_hc_cdict_search_kernel + "
@@ -910,6 +933,59 @@ int APE_LZ4_compress_hc_opt_usingCDict_batch_dev(const char *const *d_src, const
 }
 
 // ---- dictionary training (lz4_dict_train.hip) ----
+// ---- a prepared dictionary per message (ape_lz4_cdicts.h) ----
+int APE_LZ4_cdict_prepare_batch_dev(const char *const *d_dict, const int *d_dictSize,
+                                    int maxSrcSize, void *d_cdicts, size_t cdict_stride,
+                                    int ndicts, void *stream) {
+    if (int rc = ready_prepare_batch("cdict_prepare_batch_dev", d_dict, d_dictSize, maxSrcSize,
+                                     d_cdicts, cdict_stride, ndicts, kCdSize))
+        return rc;
+    return finish_launch(launch_cdict_prepare_batch(d_dict, d_dictSize, maxSrcSize, d_cdicts,
+                                                    cdict_stride, ndicts, (hipStream_t)stream),
+                         "lz4_cdict_prepare_batch_kernel");
+}
+
+int APE_LZ4_hc_cdict_prepare_batch_dev(const char *const *d_dict, const int *d_dictSize,
+                                       int maxSrcSize, void *d_cdicts, size_t cdict_stride,
+                                       int ndicts, void *stream) {
+    if (int rc = ready_prepare_batch("hc_cdict_prepare_batch_dev", d_dict, d_dictSize, maxSrcSize,
+                                     d_cdicts, cdict_stride, ndicts, kHdSize))
+        return rc;
+    return finish_launch(launch_hc_cdict_prepare_batch(d_dict, d_dictSize, maxSrcSize, d_cdicts,
+                                                       cdict_stride, ndicts, (hipStream_t)stream),
+                         "lz4_hc_cdict_prepare_batch_kernel");
+}
+
+int APE_LZ4_compress_usingCDicts_batch_dev(const char *const *d_src, const int *d_srcSize,
+                                           char *const *d_dst, const int *d_dstCap, int *d_result,
+                                           int nblocks, const void *const *d_cdict, void *stream) {
+    const BlockArgs a = ptr_args(d_src, d_srcSize, d_dst, d_dstCap, nullptr, d_result, nblocks);
+    if (int rc = ready_ptr("compress_usingCDicts_batch_dev", a, {d_cdict})) return rc;
+    return finish_launch(launch_encode_cdicts(a, d_cdict, (hipStream_t)stream),
+                         "lz4_encode_cdicts_kernel");
+}
+
+int APE_LZ4_compress_hc_usingCDicts_batch_dev(const char *const *d_src, const int *d_srcSize,
+                                              char *const *d_dst, const int *d_dstCap,
+                                              int *d_result, int nblocks,
+                                              const void *const *d_cdict, int maxSrcSize, int depth,
+                                              void *d_scratch, size_t scratch_bytes, void *stream) {
+    return hc_cdict_batch("compress_hc_usingCDicts_batch_dev", false, d_src, d_srcSize, d_dst,
+                          d_dstCap, d_result, nblocks, nullptr, maxSrcSize, depth, d_scratch,
+                          scratch_bytes, stream, d_cdict, true);
+}
+
+int APE_LZ4_compress_hc_opt_usingCDicts_batch_dev(const char *const *d_src, const int *d_srcSize,
+                                                  char *const *d_dst, const int *d_dstCap,
+                                                  int *d_result, int nblocks,
+                                                  const void *const *d_cdict, int maxSrcSize,
+                                                  int depth, void *d_scratch, size_t scratch_bytes,
+                                                  void *stream) {
+    return hc_cdict_batch("compress_hc_opt_usingCDicts_batch_dev", true, d_src, d_srcSize, d_dst,
+                          d_dstCap, d_result, nblocks, nullptr, maxSrcSize, depth, d_scratch,
+                          scratch_bytes, stream, d_cdict, true);
+}
+
 size_t APE_LZ4_dict_train_scratch_size(int nsamples, int maxSampleSize, int segmentSize) {
     if (!dt_shape_ok(nsamples, maxSampleSize, segmentSize)) return 0;
     return dt_scratch_bytes(nsamples, maxSampleSize, segmentSize);
