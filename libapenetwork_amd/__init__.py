@@ -131,6 +131,13 @@ def lib():
             "APE_LZ4_compress_large_hc_scratch_size": (sz, [i, i, i]),
             "APE_LZ4_compress_large_hc_batch_dev": (i, [p, p, p, p, p, i, i, i, p, sz, i, p, sz, p]),
             "APE_LZ4_compress_large_hc_timed_dev": (i, [p, p, p, p, p, i, i, i, p, sz, i, p, p]),
+            "APE_LZ4_xxh32_batch_dev": (i, [p, p, _C.c_uint, p, i, p]),
+            "APE_LZ4_lz4f_compress_bound": (sz, [i, i]),
+            "APE_LZ4_lz4f_compress_scratch_size": (sz, [i, i]),
+            "APE_LZ4_lz4f_compress_batch_dev": (i, [p, p, p, p, p, i, i, i, p, sz, p]),
+            "APE_LZ4_lz4f_info_batch_dev": (i, [p, p, p, i, p]),
+            "APE_LZ4_lz4f_decompress_scratch_size": (sz, [i, i]),
+            "APE_LZ4_lz4f_decompress_batch_dev": (i, [p, p, p, p, p, i, i, i, p, sz, p]),
             "APE_LZ4_rxbuf_new": (p, [sz]),
             "APE_LZ4_rxbuf_prepare": (i, [p, sz]),
             "APE_LZ4_rxbuf_append": (i, [p, p, sz]),
@@ -1103,6 +1110,82 @@ class Chain:
             self.free()
         except Exception:
             pass
+
+
+# ---- the LZ4 frame format (include/ape_lz4f.h) ----
+# (Public without a line in __all__, as the calls of ape_lz4_cdicts.h are; tests/test_lz4f_args.py
+# checks these seven.)
+LZ4F_CONTENT_CHECKSUM, LZ4F_BLOCK_CHECKSUMS, LZ4F_CONTENT_SIZE = 1, 2, 4   # compress flags
+LZ4F_NO_VERIFY, LZ4F_NO_LINKED = 1, 2                                     # decompress flags
+
+
+def xxh32_batch(src_ptrs, sizes, hashes, seed=0, stream=None):
+    """APE_LZ4_xxh32_batch_dev: hashes[i] (int32 CUDA tensor, the hash's 32 bits) = XXH32 with
+    `seed` of the max(sizes[i], 0) bytes at src_ptrs[i] (int64 CUDA tensor of pointers)."""
+    what = "xxh32_batch"
+    if not isinstance(seed, int) or isinstance(seed, bool) or not 0 <= seed < 1 << 32:
+        raise ValueError("%s seed: need an int in [0, 2^32)" % what)
+    n = _count(what, "sizes", sizes)
+    _ptr_args(what, n, src_ptrs=src_ptrs, sizes=sizes, hashes=hashes)
+    _call("APE_LZ4_xxh32_batch_dev", _ptr(src_ptrs), _ptr(sizes), seed, _ptr(hashes), n,
+          _stream(stream))
+
+
+def lz4f_compress_bound(src_size, flags=0):
+    """APE_LZ4_lz4f_compress_bound: the most bytes a frame of src_size input bytes takes with
+    these flags (0 for arguments out of range)."""
+    return lib().APE_LZ4_lz4f_compress_bound(src_size, flags)
+
+
+def lz4f_compress_scratch_size(nframes, max_src_size):
+    """APE_LZ4_lz4f_compress_scratch_size: scratch bytes of one lz4f_compress_batch call."""
+    return lib().APE_LZ4_lz4f_compress_scratch_size(nframes, max_src_size)
+
+
+def lz4f_decompress_scratch_size(nframes, max_blocks):
+    """APE_LZ4_lz4f_decompress_scratch_size: scratch bytes of one lz4f_decompress_batch call."""
+    return lib().APE_LZ4_lz4f_decompress_scratch_size(nframes, max_blocks)
+
+
+def _lz4f_batch(symbol, what, src_ptrs, sizes, dst_ptrs, caps, results, limit, flags, scratch,
+                stream):
+    """Both framed calls: the five arrays, a limit per frame, flags, the scratch."""
+    n = _ptr_batch(what, _FIVE, src_ptrs, sizes, dst_ptrs, caps, results)
+    _bytes(scratch, what + " scratch")
+    _call(symbol, _ptr(src_ptrs), _ptr(sizes), _ptr(dst_ptrs), _ptr(caps), _ptr(results), n, limit,
+          flags, _ptr(scratch), scratch.numel(), _stream(stream))
+
+
+def lz4f_compress_batch(src_ptrs, src_sizes, dst_ptrs, caps, results, max_src_size, flags,
+                        scratch, stream=None):
+    """APE_LZ4_lz4f_compress_batch_dev: input i -> one LZ4 frame (64 KiB independent blocks;
+    flags: LZ4F_CONTENT_CHECKSUM | LZ4F_BLOCK_CHECKSUMS | LZ4F_CONTENT_SIZE) at dst_ptrs[i];
+    results[i] = the frame's bytes, 0 when it does not fit caps[i] (nothing written), ERANGE
+    above max_src_size.  Pointer-array form; scratch: uint8 CUDA tensor of at least
+    lz4f_compress_scratch_size(N, max_src_size) bytes, 16-byte aligned.  Allocates nothing."""
+    _lz4f_batch("APE_LZ4_lz4f_compress_batch_dev", "lz4f_compress_batch", src_ptrs, src_sizes,
+                dst_ptrs, caps, results, max_src_size, flags, scratch, stream)
+
+
+def lz4f_decompress_batch(src_ptrs, src_sizes, dst_ptrs, caps, results, max_blocks, flags,
+                          scratch, stream=None):
+    """APE_LZ4_lz4f_decompress_batch_dev: frame i (of up to max_blocks blocks) -> its content at
+    dst_ptrs[i]; results[i] = the decoded size or a negative code (include/ape_lz4f.h; flags:
+    LZ4F_NO_VERIFY | LZ4F_NO_LINKED).  Pointer-array form; scratch: uint8 CUDA tensor of at least
+    lz4f_decompress_scratch_size(N, max_blocks) bytes, 16-byte aligned.  Allocates nothing."""
+    _lz4f_batch("APE_LZ4_lz4f_decompress_batch_dev", "lz4f_decompress_batch", src_ptrs, src_sizes,
+                dst_ptrs, caps, results, max_blocks, flags, scratch, stream)
+
+
+def lz4f_info_batch(src_ptrs, src_sizes, info, stream=None):
+    """APE_LZ4_lz4f_info_batch_dev: info (int32 CUDA tensor of 8 N) gets, per frame, {code, FLG,
+    block maximum, blocks, frame bytes, decoded bound, content size low, high (or -1, -1)}."""
+    what = "lz4f_info_batch"
+    n = _count(what, "src_sizes", src_sizes)
+    _ptr_args(what, n, src_ptrs=src_ptrs, src_sizes=src_sizes)
+    _ptr_args(what, 8 * n, info=info)
+    _call("APE_LZ4_lz4f_info_batch_dev", _ptr(src_ptrs), _ptr(src_sizes), _ptr(info), n,
+          _stream(stream))
 
 
 SOCKET_STATS = {"tx_h2d_ms": 0, "tx_encode_ms": 1, "tx_d2h_ms": 2, "tx_write_ms": 3,

@@ -510,4 +510,67 @@ hipError_t launch_large_hc(const LargeArgs &a, int depth, void *hc, int pass, hi
 hipError_t launch_synth(char *out, size_t stride, int n, long long first, int nblocks,
                         int kind, hipStream_t s);
 
+// ---- the LZ4 frame format (lz4_lz4f.hip, include/ape_lz4f.h) ----
+// hash[i] = XXH32(src[i][0, max(size[i], 0)), seed): one launch, 16 streams per wave
+hipError_t launch_xxh32(const char *const *src, const int *size, uint32_t seed, uint32_t *hash,
+                        int n, hipStream_t s);
+constexpr int kLfMaxSrc = 0x7E000000;
+constexpr int kLfHeaderMax = 15, kLfHeaderMin = 7;   // with and without the content size
+// Framed compress: the caller's arrays, and the scratch cut into per-slot arrays (slot = frame
+// f, block q at f * bpf + q) by lz4f_compress_layout.
+struct LfCompress {
+    const char *const *src;   // caller's arrays, one entry per frame
+    const int *src_size;
+    char *const *dst;
+    const int *dst_cap;
+    int *result;
+    int nframes, max_src, flags;
+    int bpf, nslots;          // slots per frame, slots in all
+    char *buf;                // slot buffers of 64 KiB (the scratch base before the layout)
+    const char **s_src;       // the encoder's arguments, one entry per slot ...
+    char **s_dst;
+    int *s_size, *s_cap, *s_res;   // ... and its results
+    uint32_t *s_off, *s_hash;      // the block's place in its frame; its checksum
+    int *f_total;             // per frame: the frame's bytes, 0 when nothing is to be written
+    uint32_t *f_hash;         // per frame: the content checksum
+};
+// fills out's scratch fields from out->buf (out nullable); (size_t)-1 from 2^24 slots on
+size_t lz4f_compress_layout(int nframes, int max_src, LfCompress *out);
+// plan, encode, layout, hash (with a checksum flag), pack: 4 or 5 launches
+hipError_t launch_lz4f_compress(const LfCompress &c, hipStream_t s);
+hipError_t launch_lz4f_info(const char *const *src, const int *src_size, int *info, int nframes,
+                            hipStream_t s);
+// Framed decode: what the plan launch found out about a frame ...
+struct LfFrame {
+    int code, nb;             // the header stage's code (0: go on); blocks
+    uint32_t bmax, flg;       // block maximum; FLG
+    uint32_t content;         // content size, with that bit in flg
+    uint32_t want, got;       // content checksum: the frame's, and the output's
+    uint32_t pad_;            // never written or read: keeps the records 32 bytes apart
+};
+static_assert(sizeof(LfFrame) % 16 == 0, "scratch regions");
+// ... and the per-slot arrays (slot = block q of frame f at q * nframes + f): the arguments of
+// launch_decode (_a: blocks of block-independent frames) and launch_decode_chain (_b: blocks of
+// linked frames, with the output before them as dictionary), and what the other launches need.
+struct LfDecode {
+    const char *const *src;   // caller's arrays, one entry per frame
+    const int *src_size;
+    char *const *dst;
+    const int *dst_cap;
+    int *result;
+    int nframes, max_blocks;
+    bool verify, no_linked;   // decompress flags bit 0 clear; bit 1 set
+    const char *zero;         // 16 bytes, the first 0 (the scratch base before the layout)
+    LfFrame *frame;
+    const char **src_a, **src_b, **dict, **data;   // data: the block's bytes in the frame
+    char **out;               // where the block's output goes
+    int *size_a, *cap_a, *res_a, *size_b, *cap_b, *res_b, *dict_size;
+    int *size, *kind, *cap;   // the block's bytes in the frame; kLf...; its room in dst
+    uint32_t *want, *got;     // block checksum: the frame's, and the bytes'
+};
+size_t lz4f_decode_layout(int nframes, int max_blocks, LfDecode *out);
+// plan, stored copies, decode, chained decode (unless no_linked), hash (when verify), finish:
+// 4 to 6 launches
+hipError_t launch_lz4f_decode(const LfDecode &d, hipStream_t s);
+
 }  // namespace apelz4

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/ape_lz4_gpu.h"
+#include "../../include/ape_lz4f.h"
 #include "lz4_gpu_internal.h"
 #include "lz4_gpu_shim.h"
 
@@ -1291,6 +1292,97 @@ int APE_LZ4_synth_blocks_dev(char *d_out, size_t stride, int blockSize, long lon
     return finish_launch(launch_synth(d_out, stride, blockSize, first_block, nblocks, kind,
                                       (hipStream_t)stream),
                          "lz4_synth_kernel");
+}
+
+// ---- the LZ4 frame format (include/ape_lz4f.h, lz4_lz4f.hip) ----
+int APE_LZ4_xxh32_batch_dev(const char *const *d_src, const int *d_size, unsigned seed,
+                            unsigned *d_hash, int n, void *stream) {
+    if (int rc = check_arrays("xxh32_batch_dev", n, {d_src, d_size, d_hash})) return rc;
+    if (int rc = check_device()) return rc;
+    return finish_launch(launch_xxh32(d_src, d_size, seed, d_hash, n, (hipStream_t)stream),
+                         "xxh32_batch_kernel");
+}
+
+size_t APE_LZ4_lz4f_compress_bound(int srcSize, int flags) {
+    if (srcSize < 0 || srcSize > kLfMaxSrc || (flags & ~7)) return 0;
+    const size_t nb = ((size_t)srcSize + kMaxBlock - 1) / kMaxBlock;
+    return (size_t)((flags & 4) ? kLfHeaderMax : kLfHeaderMin) + (size_t)srcSize +
+           nb * ((flags & 2) ? 8 : 4) + ((flags & 1) ? 8 : 4);
+}
+
+size_t APE_LZ4_lz4f_compress_scratch_size(int nframes, int maxSrcSize) {
+    if (nframes < 0 || maxSrcSize < 0 || maxSrcSize > kLfMaxSrc) return 0;
+    return lz4f_compress_layout(nframes, maxSrcSize, nullptr);
+}
+
+int APE_LZ4_lz4f_compress_batch_dev(const char *const *d_src, const int *d_srcSize,
+                                    char *const *d_dst, const int *d_dstCap, int *d_result,
+                                    int nframes, int maxSrcSize, int flags, void *d_scratch,
+                                    size_t scratch_bytes, void *stream) {
+    const char *who = "lz4f_compress_batch_dev";
+    if (int rc = check_arrays(who, nframes, {d_src, d_srcSize, d_dst, d_dstCap, d_result}))
+        return rc;
+    const size_t need = APE_LZ4_lz4f_compress_scratch_size(nframes, maxSrcSize);
+    if (maxSrcSize < 0 || maxSrcSize > kLfMaxSrc || (flags & ~7) || need == (size_t)-1 ||
+        (nframes > 0 && (!d_scratch || scratch_bytes < need || !aligned16(d_scratch))))
+        return einval("%s: nframes %d, maxSrcSize %d (0..%d), flags %d (0..7), scratch of %zu "
+                      "bytes at %p (need %zu bytes 16-byte aligned, fewer than 2^24 blocks)", who,
+                      nframes, maxSrcSize, kLfMaxSrc, flags, scratch_bytes, d_scratch, need);
+    if (int rc = check_device()) return rc;
+    LfCompress c{};
+    c.src = d_src;
+    c.src_size = d_srcSize;
+    c.dst = d_dst;
+    c.dst_cap = d_dstCap;
+    c.result = d_result;
+    c.nframes = nframes;
+    c.max_src = maxSrcSize;
+    c.flags = flags;
+    c.buf = (char *)d_scratch;
+    lz4f_compress_layout(nframes, maxSrcSize, &c);
+    return finish_launch(launch_lz4f_compress(c, (hipStream_t)stream), "lz4f_compress");
+}
+
+int APE_LZ4_lz4f_info_batch_dev(const char *const *d_src, const int *d_srcSize, int *d_info,
+                                int nframes, void *stream) {
+    if (int rc = check_arrays("lz4f_info_batch_dev", nframes, {d_src, d_srcSize, d_info}))
+        return rc;
+    if (int rc = check_device()) return rc;
+    return finish_launch(launch_lz4f_info(d_src, d_srcSize, d_info, nframes, (hipStream_t)stream),
+                         "lz4f_info_kernel");
+}
+
+size_t APE_LZ4_lz4f_decompress_scratch_size(int nframes, int maxBlocks) {
+    if (nframes < 0 || maxBlocks < 1) return 0;
+    return lz4f_decode_layout(nframes, maxBlocks, nullptr);
+}
+
+int APE_LZ4_lz4f_decompress_batch_dev(const char *const *d_src, const int *d_srcSize,
+                                      char *const *d_dst, const int *d_dstCap, int *d_result,
+                                      int nframes, int maxBlocks, int flags, void *d_scratch,
+                                      size_t scratch_bytes, void *stream) {
+    const char *who = "lz4f_decompress_batch_dev";
+    if (int rc = check_arrays(who, nframes, {d_src, d_srcSize, d_dst, d_dstCap, d_result}))
+        return rc;
+    const size_t need = APE_LZ4_lz4f_decompress_scratch_size(nframes, maxBlocks);
+    if (maxBlocks < 1 || (flags & ~3) || need == (size_t)-1 || (nframes > 0 && (!d_scratch || scratch_bytes < need || !aligned16(d_scratch))))
+        return einval("%s: nframes %d, maxBlocks %d (from 1), flags %d (0..3), scratch of %zu "
+                      "bytes at %p (need %zu bytes 16-byte aligned, fewer than 2^24 blocks)", who,
+                      nframes, maxBlocks, flags, scratch_bytes, d_scratch, need);
+    if (int rc = check_device()) return rc;
+    LfDecode d{};
+    d.src = d_src;
+    d.src_size = d_srcSize;
+    d.dst = d_dst;
+    d.dst_cap = d_dstCap;
+    d.result = d_result;
+    d.nframes = nframes;
+    d.max_blocks = maxBlocks;
+    d.verify = !(flags & 1);
+    d.no_linked = (flags & 2) != 0;
+    d.zero = (const char *)d_scratch;
+    lz4f_decode_layout(nframes, maxBlocks, &d);
+    return finish_launch(launch_lz4f_decode(d, (hipStream_t)stream), "lz4f_decompress");
 }
 
 #ifdef APE_LZ4_STATS
