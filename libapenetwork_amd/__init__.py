@@ -138,6 +138,9 @@ def lib():
             "APE_LZ4_lz4f_info_batch_dev": (i, [p, p, p, i, p]),
             "APE_LZ4_lz4f_decompress_scratch_size": (sz, [i, i]),
             "APE_LZ4_lz4f_decompress_batch_dev": (i, [p, p, p, p, p, i, i, i, p, sz, p]),
+            "APE_LZ4_decompress_safe_size_batch_dev": (i, [p, p, p, p, p, i, p]),
+            "APE_LZ4_lz4f_decompress_placed_scratch_size": (sz, [i, i]),
+            "APE_LZ4_lz4f_decompress_placed_batch_dev": (i, [p, p, p, p, p, i, i, i, p, sz, p]),
             "APE_LZ4_rxbuf_new": (p, [sz]),
             "APE_LZ4_rxbuf_prepare": (i, [p, sz]),
             "APE_LZ4_rxbuf_append": (i, [p, p, sz]),
@@ -1186,6 +1189,39 @@ def lz4f_info_batch(src_ptrs, src_sizes, info, stream=None):
     _ptr_args(what, 8 * n, info=info)
     _call("APE_LZ4_lz4f_info_batch_dev", _ptr(src_ptrs), _ptr(src_sizes), _ptr(info), n,
           _stream(stream))
+
+
+# ---- frames with short blocks (include/ape_lz4f_placed.h) ----
+# (Public without a line in __all__, as the calls above; tests/test_lz4f_placed_args.py checks
+# these three.)
+def decompress_size_ptr_batch(src_ptrs, src_sizes, caps, results, dict_sizes=None, stream=None):
+    """APE_LZ4_decompress_safe_size_batch_dev: results[i] = what decompress_safe of block i
+    into caps[i] bytes would return (with dict_sizes: decompress_safe_usingDict with that many
+    bytes of dictionary) -- the decoded size or -(ip)-1 -- without a destination: nothing but
+    results is written.  Pointer-array form, int32 tensors but src_ptrs (int64)."""
+    what = "decompress_size_ptr_batch"
+    n = _count(what, "src_sizes", src_sizes)
+    _ptr_args(what, n, ("dict_sizes",), src_ptrs=src_ptrs, src_sizes=src_sizes, caps=caps,
+              results=results, dict_sizes=dict_sizes)
+    _call("APE_LZ4_decompress_safe_size_batch_dev", _ptr(src_ptrs), _ptr(src_sizes), _ptr(caps),
+          _ptr(dict_sizes), _ptr(results), n, _stream(stream))
+
+
+def lz4f_decompress_placed_scratch_size(nframes, max_blocks):
+    """APE_LZ4_lz4f_decompress_placed_scratch_size: scratch bytes of one
+    lz4f_decompress_placed_batch call."""
+    return lib().APE_LZ4_lz4f_decompress_placed_scratch_size(nframes, max_blocks)
+
+
+def lz4f_decompress_placed_batch(src_ptrs, src_sizes, dst_ptrs, caps, results, max_blocks, flags,
+                                 scratch, stream=None):
+    """APE_LZ4_lz4f_decompress_placed_batch_dev: lz4f_decompress_batch for frames whose blocks
+    may be short (a producer that flushes): every block is sized first and decoded where it
+    belongs; results[i] = the decoded size or a negative code (include/ape_lz4f_placed.h).
+    scratch: uint8 CUDA tensor of at least lz4f_decompress_placed_scratch_size(N, max_blocks)
+    bytes, 16-byte aligned.  Allocates nothing."""
+    _lz4f_batch("APE_LZ4_lz4f_decompress_placed_batch_dev", "lz4f_decompress_placed_batch",
+                src_ptrs, src_sizes, dst_ptrs, caps, results, max_blocks, flags, scratch, stream)
 
 
 SOCKET_STATS = {"tx_h2d_ms": 0, "tx_encode_ms": 1, "tx_d2h_ms": 2, "tx_write_ms": 3,

@@ -41,6 +41,10 @@
 // instantiations without the flag compile to the device code they had before it existed.
 // A byte range of such a block is read by decoding only the segments that cover it
 // (lz4_range_plan_kernel, lz4_decode_range_kernel, after the indexed kernel).
+//
+// The decoded size alone (lz4_decode_size_kernel, after the chain kernel) is the PARSE phase
+// without the COPY phase: the parse functions are templates on the LDS type, and with SizeLds
+// (the staged input alone) they keep no descriptors.  With WaveLds they compile as before.
 #include "lz4_gpu_internal.h"
 #include <type_traits>
 
@@ -77,6 +81,13 @@ struct __attribute__((aligned(16))) WaveLds {
     uint8_t win[kWinB + 64];     // output [base, base + kWinB) (+ slack for 16-byte reads)
     uint4 desc[kMaxDesc];        // {lit_src, out, lit_len, offset}
 };
+// The sizer's LDS (lz4_decode_size_kernel): the staged input alone.  The parse functions below
+// take either; with this one they keep no descriptors (kDesc).
+struct __attribute__((aligned(16))) SizeLds {
+    uint8_t stage[kStage + 16];
+};
+template <class LDS>
+constexpr bool kDesc = std::is_same<LDS, WaveLds>::value;
 
 // unaligned LDS accesses (gfx950 DS instructions take any byte address)
 typedef uint32_t l32x4 __attribute__((ext_vector_type(4), aligned(1)));
@@ -150,7 +161,8 @@ __device__ __forceinline__ uint32_t src_dword(gcu8 *src, int csize, int off, int
 }
 
 // Stage src[s0 .. s0 + kStage) into LDS (src + s0 4-aligned; zero outside the input).
-__device__ __forceinline__ void stage_load(WaveLds &L, gcu8 *src, int csize, int s0,
+template <class LDS>
+__device__ __forceinline__ void stage_load(LDS &L, gcu8 *src, int csize, int s0,
                                            int lane) {
     const int first = -(int)((uintptr_t)src & 3u);   // aligned dword holding byte 0
     uint32_t v[kStage / 256];
@@ -166,7 +178,8 @@ __device__ __forceinline__ int stage_base(gcu8 *src, int p) {
 }
 
 // byte p of the compressed block for the scalar path (wave-uniform p)
-__device__ __forceinline__ uint32_t sbyte(const WaveLds &L, gcu8 *src, int csize, int s0,
+template <class LDS>
+__device__ __forceinline__ uint32_t sbyte(const LDS &L, gcu8 *src, int csize, int s0,
                                           int p) {
     const uint32_t r = (uint32_t)(p - s0);
     if (r < (uint32_t)kStage) return L.stage[r];
@@ -213,8 +226,8 @@ constexpr int kNoStop = 0x7FFFFFFF;
 // reaches cap exactly; no input-size tests (csize is only the readable bound of src);
 // the result is the input consumed.
 // STOP (a segment of an indexed block): a token at or past D.stop is not parsed.
-template <bool PARTIAL, bool FASTD = false, bool STOP = false>
-__device__ int parse_scalar(WaveLds &L, const Dec &D, int &ip, uint32_t &op, int &nd, int &res) {
+template <bool PARTIAL, bool FASTD = false, bool STOP = false, class LDS>
+__device__ int parse_scalar(LDS &L, const Dec &D, int &ip, uint32_t &op, int &nd, int &res) {
     if (STOP && ip >= D.stop) return ST_MORE;
     const uint32_t tok = sbyte(L, D.src, D.csize, D.s0, ip);
     ip++;
@@ -237,7 +250,8 @@ __device__ int parse_scalar(WaveLds &L, const Dec &D, int &ip, uint32_t &op, int
                                : (PARTIAL ? (cpy > D.cap || (int64_t)ip + lit > D.csize)
                                           : ((int64_t)ip + lit != D.csize || cpy > D.cap));
         if (bad) { res = -ip - 1; return ST_ERR; }
-        if (D.lane == 0) L.desc[nd] = make_uint4((uint32_t)ip, op, (uint32_t)lit, 0u);
+        if constexpr (kDesc<LDS>)
+            if (D.lane == 0) L.desc[nd] = make_uint4((uint32_t)ip, op, (uint32_t)lit, 0u);
         nd++;
         op = (uint32_t)cpy;
         res = FASTD ? ip + (int)lit : (int)cpy;
@@ -263,7 +277,8 @@ __device__ int parse_scalar(WaveLds &L, const Dec &D, int &ip, uint32_t &op, int
     }
     const int64_t mend = cpy + ml + kMinMatch;
     if (mend > (int64_t)D.cap - kLastLiterals) { res = -ip - 1; return ST_ERR; }  // :1444
-    if (D.lane == 0) L.desc[nd] = make_uint4((uint32_t)lit_src, op, (uint32_t)lit, off);
+    if constexpr (kDesc<LDS>)
+        if (D.lane == 0) L.desc[nd] = make_uint4((uint32_t)lit_src, op, (uint32_t)lit, off);
     nd++;
     op = (uint32_t)mend;
     return ST_MORE;
@@ -294,8 +309,8 @@ struct Spec {
     uint32_t r1;                     // staged position after the literals (s0 + r1 = ipl + lit)
 };
 
-template <bool FASTD>
-__device__ __forceinline__ Spec spec_at(const WaveLds &L, const Dec &D, int P, uint32_t rel) {
+template <bool FASTD, class LDS>
+__device__ __forceinline__ Spec spec_at(const LDS &L, const Dec &D, int P, uint32_t rel) {
     Spec z;
     const uint32_t r = (uint32_t)(P - D.s0) + rel;
     // token and the byte after it as two byte reads (one unaligned ds_read_u16 per lane, at a
@@ -336,8 +351,8 @@ __device__ __forceinline__ Spec spec_at(const WaveLds &L, const Dec &D, int P, u
 // staged input only ever belongs to a complex lane, whose bytes do not matter).  Against the full spec_at here: -0.5 % decode time
 // (profiles/r5_decoder_hop_ab.txt).
 constexpr uint32_t kHopTerm = 0x200u, kHopCplx = 0x300u;   // chain_at's exit codes (below)
-template <bool FASTD>
-__device__ __forceinline__ uint32_t hop_at(const WaveLds &L, const Dec &D, int P, uint32_t rel) {
+template <bool FASTD, class LDS>
+__device__ __forceinline__ uint32_t hop_at(const LDS &L, const Dec &D, int P, uint32_t rel) {
     const uint32_t r = (uint32_t)(P - D.s0) + rel;
     const uint32_t tok = L.stage[r], e1 = L.stage[r + 1u];
     const bool litx = tok >= 0xF0u;
@@ -361,8 +376,8 @@ __device__ __forceinline__ uint32_t hop_at(const WaveLds &L, const Dec &D, int P
 // (lanes [0, cnt)); X = the chain's exit (next token position >= 64, or kHopTerm after a
 // final / failing sequence, kHopCplx before a complex token); lastp = the last member.
 // A real hop is < 0x200 (63 + 1 + 1 + 269 + 2 + 1); the codes are above it.
-template <bool FASTD>
-__device__ __forceinline__ void chain_at(const WaveLds &L, const Dec &D, int P, uint32_t &pos,
+template <bool FASTD, class LDS>
+__device__ __forceinline__ void chain_at(const LDS &L, const Dec &D, int P, uint32_t &pos,
                                          int &cnt, uint32_t &X, uint32_t &lastp) {
     // hop and the J_k hold window positions x 4: ds_bpermute's byte address (it uses
     // address bits [7:2] only), so an exit (>= 64, i.e. >= 256 here) needs no mask
@@ -417,8 +432,8 @@ __device__ __forceinline__ void chain_at(const WaveLds &L, const Dec &D, int P, 
 // its sequence from the staged bytes.
 // STOP: the members end before the first one whose token lies at or past D.stop, and P
 // becomes that token's position (the caller compares it with the stop).
-template <bool PARTIAL, bool DICT, bool FASTD = false, bool STOP = false>
-__device__ int parse_window(WaveLds &L, const Dec &D, int &P, uint32_t &op, int &nd, int &res,
+template <bool PARTIAL, bool DICT, bool FASTD = false, bool STOP = false, class LDS>
+__device__ int parse_window(LDS &L, const Dec &D, int &P, uint32_t &op, int &nd, int &res,
                             bool &cplx) {
     const int lane = D.lane;
     const uint32_t t = (uint32_t)lane;
@@ -548,7 +563,8 @@ __device__ int parse_window(WaveLds &L, const Dec &D, int &P, uint32_t &op, int 
     }
     if (st != ST_ERR) {
         const int ne = __popcll(emit);
-        if ((int)t < ne) L.desc[nd + lane] = make_uint4((uint32_t)ipl, opl, lit, fin ? 0u : off);
+        if constexpr (kDesc<LDS>)
+            if ((int)t < ne) L.desc[nd + lane] = make_uint4((uint32_t)ipl, opl, lit, fin ? 0u : off);
         nd += ne;
         if (ne) {
             // a final sequence's size is its literals (ob assumed a match unless the
@@ -1231,6 +1247,97 @@ lz4_decode_chain_kernel(BlockArgs a, int nconn, int nq) {
     }
 }
 
+// ---- the decoded size alone (include/ape_lz4f_placed.h) ----
+// decode_block's parse half as a dry run: the special cases, the single literal run and the
+// parse_window / parse_scalar chain with their checks, so that the result is the value
+// decompress_safe (with a.dict_size: _usingDict with that many bytes of history) returns --
+// but no output window, no descriptors, no destination.  Only the running output position and
+// the first failing sequence are kept; the LDS is the staged input.  Nothing but a.result[b] is
+// written.
+__global__ void __launch_bounds__(64)
+lz4_decode_size_kernel(BlockArgs a) {
+    __shared__ SizeLds L;
+    const int b = (int)blockIdx.x, lane = (int)threadIdx.x;
+    Dec D;
+    D.src = (gcu8 *)a.src[b];
+    D.dst = nullptr;
+    D.dend = nullptr;
+    D.csize = a.src_size[b];
+    D.cap = a.dst_cap[b];
+    D.oexit = 0;
+    D.stop = kNoStop;
+    D.lane = lane;
+    for (int k = 0; k < 5; ++k) {
+        uint32_t m = 0u - (((uint32_t)lane >> k) & 1u);
+        asm volatile("" : "+v"(m));   // (as decode_block)
+        D.mk[k] = m;
+    }
+    const int ds = a.dict_size ? a.dict_size[b] : 0;
+    D.dsz = ds <= 0 ? 0u : ds < 65536 ? (uint32_t)ds : 65536u;
+
+    // the special cases at the top of decode_block
+    if (D.cap == 0 || D.csize <= 0) {
+        if (lane == 0) {
+            int r;
+            if (D.cap == 0) r = (D.csize == 1 && D.src[0] == 0) ? 0 : -1;
+            else r = ((D.src ? D.src[0] : 0u) >= 0xF0) ? -3 : -2;
+            a.result[b] = r;
+        }
+        return;
+    }
+    // one literal run holding the whole block: the length bytes, 64 at a time (as decode_block;
+    // the final-literals branch asks nothing of the history, so this holds with one too)
+    if (D.csize >= 32 && D.cap > 0 && D.src[0] >= 0xF0u) {
+        int J = 0;
+        for (int base = 1;; base += 64) {
+            const int i = base + lane;
+            const uint32_t byte = D.src[i < D.csize ? i : D.csize - 1];   // (never past src)
+            const bool stop = i + 1 >= D.csize - 15 || byte != 255u;
+            const uint64_t m = wave_ballot(stop);
+            if (m) {
+                J = base + __builtin_ctzll(m);
+                break;
+            }
+        }
+        const long long run = 15ll + 255ll * (J - 1) + (long long)D.src[J];
+        if ((long long)J + 1 + run == (long long)D.csize) {
+            if (lane == 0) a.result[b] = run > (long long)D.cap ? -(J + 1) - 1 : (int)run;
+            return;
+        }
+    }
+
+    int P = 0, nd = 0, result = 0, st = ST_MORE;
+    uint32_t op = 0;
+    if (lane < 4) *(uint32_t *)&L.stage[kStage + 4 * lane] = 0u;  // over-read pad
+    D.s0 = stage_base(D.src, 0);
+    stage_load(L, D.src, D.csize, D.s0, lane);
+    wave_sync();
+    if (D.cap < 0) {   // (as decode_block: the first sequence's final-literals test fails)
+        (void)parse_scalar<false, false>(L, D, P, op, nd, result);
+        if (lane == 0) a.result[b] = result;
+        return;
+    }
+    for (;;) {
+        while (st == ST_MORE && P - D.s0 + kWinNeed <= kStage) {
+            bool cplx;
+            nd = 0;   // no descriptors are held: every window may take its three chains
+            st = parse_window<false, true>(L, D, P, op, nd, result, cplx);
+            if (st == ST_MORE && cplx) st = parse_scalar<false, false>(L, D, P, op, nd, result);
+        }
+        if (st != ST_MORE) break;
+        wave_sync();
+        D.s0 = stage_base(D.src, P);
+        stage_load(L, D.src, D.csize, D.s0, lane);
+        wave_sync();
+    }
+    if (lane == 0) a.result[b] = result;
+}
+
+hipError_t launch_decode_size(const BlockArgs &a, hipStream_t s) {
+    if (a.nblocks <= 0) return hipSuccess;
+    hipLaunchKernelGGL(lz4_decode_size_kernel, dim3(a.nblocks), dim3(64), 0, s, a);
+    return hipGetLastError();
+}
 
 // ---- indexed blocks (include/ape_lz4_gpu.h, "large blocks with restart points and a seek
 // index") ----

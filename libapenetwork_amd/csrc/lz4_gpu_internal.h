@@ -573,4 +573,21 @@ size_t lz4f_decode_layout(int nframes, int max_blocks, LfDecode *out);
 // 4 to 6 launches
 hipError_t launch_lz4f_decode(const LfDecode &d, hipStream_t s);
 
+// ---- frames with short blocks (include/ape_lz4f_placed.h) ----
+// result[i] = what decompress_safe (with a.dict_size: _usingDict) would return for block i, by
+// a dry run of the decoder's parse: a.src, a.src_size, a.dst_cap, a.dict_size (nullable) and
+// a.result are used, and nothing but a.result is written (lz4_decode.hip)
+hipError_t launch_decode_size(const BlockArgs &a, hipStream_t s);
+// The placed framed decode: LfDecode's arrays, with `cap` holding a block's measured size once
+// the place launch has run, and what the sizer needs besides.
+struct LfPlaced {
+    LfDecode d;
+    int *cap_s, *res_s;       // the sizer's capacity (the block maximum; 0: not sized) and result
+    int *total;               // per frame: the sum of the measured sizes, once the frame is placed
+};
+size_t lz4f_placed_layout(int nframes, int max_blocks, LfPlaced *out);
+// plan, size, place, stored copies, decode, chained decode (unless no_linked), hash (when
+// verify), finish: 6 to 8 launches
+hipError_t launch_lz4f_placed(const LfPlaced &p, hipStream_t s);
+
 }  // namespace apelz4

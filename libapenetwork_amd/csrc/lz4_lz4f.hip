@@ -3,6 +3,8 @@
 // launchers (launch_encode, launch_decode, launch_decode_chain); this file plans their
 // pointer arrays in the caller's scratch, hashes, and packs or judges the frames.
 // tests/lz4fmodel.py is the definition of the frame bytes and of the decoder's codes.
+// The placed decode (include/ape_lz4f_placed.h; tests/lz4fplacedmodel.py) sizes
+// every block with launch_decode_size before it places and decodes them.
 #include "lz4_gpu_internal.h"
 
 namespace apelz4 {
@@ -534,6 +536,182 @@ lz4f_decode_finish_kernel(LfDecode d) {
     if (lane == 0u) d.result[f] = code;
 }
 
+// ---- decode, blocks of any size (include/ape_lz4f_placed.h) ----
+// tests/lz4fplacedmodel.py is the definition of the codes.  The per-slot arrays are LfDecode's;
+// `cap` becomes the block's measured size, which is also the room its decoder gets.
+__device__ __forceinline__ void lfp_absent(const LfPlaced &p, uint32_t i) {
+    lfd_absent(p.d, i);
+    p.cap_s[i] = 0;
+}
+
+// one wave per frame: as lz4f_decode_plan_kernel, but where a block goes is not known yet.  A
+// compressed block gets its sizer arguments: the block maximum as capacity, and for a linked
+// frame 65536 bytes of assumed history (the decoded size does not depend on the offsets; the
+// real decode applies the true test).
+__global__ void __launch_bounds__(64)
+lz4f_placed_plan_kernel(LfPlaced p) {
+    const LfDecode &d = p.d;
+    const uint32_t f = blockIdx.x, lane = (uint32_t)lane_id(), nf = (uint32_t)d.nframes;
+    uint32_t filled = 0u;
+    if (lane == 0u) {
+        *(uint8_t *)d.zero = 0u;   // (as lz4f_decode_plan_kernel)
+        gcu8 *s = (gcu8 *)d.src[f];
+        const int n = d.src_size[f];
+        const LfHead h = lf_header(s, n, d.no_linked);
+        uint32_t nb = 0u, bytes = 0u, bound = 0u;
+        int walk = 0;
+        if (!h.code)
+            walk = lf_walk(s, n, h, [&](uint32_t q, uint32_t at, uint32_t w) {
+                if (q >= (uint32_t)d.max_blocks) return;
+                const uint32_t i = q * nf + f, sz = w & 0x7FFFFFFFu;
+                lfp_absent(p, i);
+                d.data[i] = (const char *)s + at;
+                d.size[i] = (int)sz;
+                if (h.flg & kFlgBlockSum) d.want[i] = gload4(s + at + sz);
+                if (w >> 31) {
+                    d.kind[i] = kLfStored;
+                } else if (h.flg & kFlgLinkedOff) {
+                    d.kind[i] = kLfIndep;
+                    d.src_a[i] = (const char *)s + at;
+                    d.size_a[i] = (int)sz;
+                    p.cap_s[i] = (int)h.bmax;
+                } else {
+                    d.kind[i] = kLfLinked;
+                    d.src_b[i] = (const char *)s + at;
+                    d.size_b[i] = (int)sz;
+                    d.dict_size[i] = 65536;
+                    p.cap_s[i] = (int)h.bmax;
+                }
+            }, &nb, &bytes);
+        int code = lf_bound(h, walk, nb, &bound);
+        if (!code && nb > (uint32_t)d.max_blocks) code = kErange;
+        LfFrame &r = d.frame[f];
+        r.code = code;
+        r.nb = (int)nb;
+        r.bmax = h.bmax;
+        r.flg = h.flg;
+        r.content = h.cs_lo;
+        r.want = (h.flg & kFlgContentSum) && !code ? gload4(s + bytes - 4u) : 0u;
+        r.got = 0u;
+        p.total[f] = 0;
+        filled = code ? 0u : nb;
+    }
+    filled = wave_first(filled);
+    for (uint32_t q = filled + lane; q < (uint32_t)d.max_blocks; q += 64u) lfp_absent(p, q * nf + f);
+}
+
+// the bytes block i of a planned frame decodes to, or -1: a stored block's length, else what
+// the sizer found
+__device__ __forceinline__ int lfp_measured(const LfPlaced &p, uint32_t i) {
+    return p.d.kind[i] == kLfStored ? p.d.size[i] : p.res_s[i];
+}
+
+// One wave per frame: the sizes scanned into positions and the total.  What can be decided is
+// decided here, before a byte of the destination is written: a block without a size (-4), a
+// total above the capacity (-9), a declared content size that is not the total (-8).  Such a
+// frame's slots become absent; the others get their place, out = dst + pos, a room of exactly
+// the measured size, and for a linked block the output before it as dictionary.
+__global__ void __launch_bounds__(64)
+lz4f_placed_place_kernel(LfPlaced p) {
+    const LfDecode &d = p.d;
+    const uint32_t f = blockIdx.x, lane = (uint32_t)lane_id(), nf = (uint32_t)d.nframes;
+    LfFrame &r = d.frame[f];
+    if (r.code) return;   // (its slots are absent since the plan)
+    const uint32_t nb = (uint32_t)r.nb;
+    const int cap = d.dst_cap[f];
+    // (a chunk of 64 blocks sums to at most 2^28; the total is kept in 64 bits)
+    uint64_t total = 0u;
+    bool unsized = false;
+    for (uint32_t q0 = 0; q0 < nb; q0 += 64u) {
+        const uint32_t q = q0 + lane;
+        const int m = q < nb ? lfp_measured(p, q * nf + f) : 0;
+        unsized |= m < 0;
+        total += lane_val(wave_incl_sum(m > 0 ? (uint32_t)m : 0u), 63);
+    }
+    int code = 0;
+    if (wave_any(unsized)) code = -4;
+    else if (cap < 0 || total > (uint64_t)cap) code = -9;
+    else if ((r.flg & kFlgSize) && (uint64_t)r.content != total) code = -8;
+    if (code) {
+        for (uint32_t q = lane; q < nb; q += 64u) lfp_absent(p, q * nf + f);
+        if (lane == 0u) r.code = code;
+        return;
+    }
+    char *const out = wave_uniform(d.dst[f]);
+    uint32_t at = 0u;   // (total <= cap < 2^31)
+    for (uint32_t q0 = 0; q0 < nb; q0 += 64u) {
+        const uint32_t q = q0 + lane, i = q * nf + f;
+        const uint32_t m = q < nb ? (uint32_t)lfp_measured(p, i) : 0u;
+        const uint32_t incl = wave_incl_sum(m);
+        if (q < nb) {
+            const uint32_t pos = at + incl - m;
+            const int kind = d.kind[i];
+            d.out[i] = out + pos;
+            d.cap[i] = (int)m;
+            if (kind == kLfIndep) {
+                d.cap_a[i] = (int)m;
+            } else if (kind == kLfLinked) {
+                const uint32_t back = umin(pos, 65536u);
+                d.cap_b[i] = (int)m;
+                d.dict[i] = out + pos - back;
+                d.dict_size[i] = (int)back;
+            }
+        }
+        at += lane_val(incl, 63);
+    }
+    if (lane == 0u) p.total[f] = (int)total;
+}
+
+__global__ void __launch_bounds__(64)
+lz4f_placed_hash_kernel(LfPlaced p) {
+    __shared__ __attribute__((aligned(16))) uint8_t lds[kXhLds];
+    const LfDecode &d = p.d;
+    const uint32_t nslots = (uint32_t)d.nframes * (uint32_t)d.max_blocks;
+    xxh32_group(lds, [&](uint32_t i) {
+        const uint32_t f = i < nslots ? i % (uint32_t)d.nframes : i - nslots;
+        LfFrame *const r = d.frame + f;
+        XStream st{nullptr, 0u, nullptr};
+        if (r->code) {
+            // nothing of a frame with a code is hashed
+        } else if (i < nslots) {   // a block, as it sits in the frame
+            if ((r->flg & kFlgBlockSum) && d.kind[i] != kLfAbsent) {
+                st.p = (gcu8 *)d.data[i];
+                st.n = (uint32_t)d.size[i];
+                st.out = d.got + i;
+            }
+        } else if (r->flg & kFlgContentSum) {   // the content: [0, total), inside the capacity
+            st.p = (gcu8 *)d.dst[f];
+            st.n = (uint32_t)p.total[f];
+            st.out = &r->got;
+        }
+        return st;
+    }, blockIdx.x * (uint32_t)kXhStreams, nslots + (uint32_t)d.nframes, 0u);
+}
+
+// one wave per frame: the place launch's code, else the first of -6, -4, -7, else the total
+__global__ void __launch_bounds__(64)
+lz4f_placed_finish_kernel(LfPlaced p) {
+    const LfDecode &d = p.d;
+    const uint32_t f = blockIdx.x, lane = (uint32_t)lane_id(), nf = (uint32_t)d.nframes;
+    const LfFrame r = d.frame[f];
+    int code = r.code;
+    if (!code) {
+        const uint32_t nb = (uint32_t)r.nb;
+        const bool sums = d.verify && (r.flg & kFlgBlockSum);
+        bool bad_sum = false, bad_block = false;
+        for (uint32_t q = lane; q < nb; q += 64u) {
+            const uint32_t i = q * nf + f;
+            bad_sum |= sums && d.got[i] != d.want[i];
+            bad_block |= lfd_block_result(d, i) != d.cap[i];   // (not what was measured)
+        }
+        if (wave_any(bad_sum)) code = -6;
+        else if (wave_any(bad_block)) code = -4;
+        else if (d.verify && (r.flg & kFlgContentSum) && r.got != r.want) code = -7;
+        else code = p.total[f];
+    }
+    if (lane == 0u) d.result[f] = code;
+}
+
 }  // namespace
 
 // ---- launchers ----
@@ -681,6 +859,71 @@ hipError_t launch_lz4f_decode(const LfDecode &d, hipStream_t s) {
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     hipLaunchKernelGGL(lz4f_decode_finish_kernel, dim3((unsigned)d.nframes), dim3(64), 0, s, d);
+    return hipGetLastError();
+}
+
+// lz4f_decode_layout's regions, then the sizer's two arrays per slot and the totals per frame
+size_t lz4f_placed_layout(int nframes, int max_blocks, LfPlaced *out) {
+    const size_t base = lz4f_decode_layout(nframes, max_blocks, out ? &out->d : nullptr);
+    if (base == (size_t)-1) return base;
+    auto up = [](size_t x) { return (x + 15) & ~(size_t)15; };
+    const size_t slots = up((size_t)nframes * (size_t)max_blocks * 4);
+    if (out) {
+        // (the layout has moved d.zero from the scratch base to its first region, at offset 0)
+        char *b = (char *)out->d.zero + base;
+        out->cap_s = (int *)b;
+        out->res_s = (int *)(b + slots);
+        out->total = (int *)(b + 2 * slots);
+    }
+    return base + 2 * slots + up((size_t)nframes * 4);
+}
+
+hipError_t launch_lz4f_placed(const LfPlaced &p, hipStream_t s) {
+    const LfDecode &d = p.d;
+    if (d.nframes <= 0) return hipSuccess;
+    hipError_t e;
+    const int nslots = d.nframes * d.max_blocks;
+    hipLaunchKernelGGL(lz4f_placed_plan_kernel, dim3((unsigned)d.nframes), dim3(64), 0, s, p);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    BlockArgs z{};   // every slot: a stored or absent one has capacity 0 and ends at once
+    z.src = d.data;
+    z.src_size = d.size;
+    z.dst_cap = p.cap_s;
+    z.dict_size = d.dict_size;
+    z.result = p.res_s;
+    z.nblocks = nslots;
+    if ((e = launch_decode_size(z, s)) != hipSuccess) return e;
+    hipLaunchKernelGGL(lz4f_placed_place_kernel, dim3((unsigned)d.nframes), dim3(64), 0, s, p);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(lz4f_decode_stored_kernel, dim3((unsigned)nslots), dim3(64), 0, s, d);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    BlockArgs a{};
+    a.src = d.src_a;
+    a.dst = d.out;
+    a.src_size = d.size_a;
+    a.dst_cap = d.cap_a;
+    a.result = d.res_a;
+    a.nblocks = nslots;
+    if ((e = launch_decode(a, false, s)) != hipSuccess) return e;
+    if (!d.no_linked) {
+        BlockArgs b{};
+        b.src = d.src_b;
+        b.dst = d.out;
+        b.src_size = d.size_b;
+        b.dst_cap = d.cap_b;
+        b.dict = d.dict;
+        b.dict_size = d.dict_size;
+        b.result = d.res_b;
+        b.nblocks = nslots;
+        if ((e = launch_decode_chain(b, d.nframes, d.max_blocks, s)) != hipSuccess) return e;
+    }
+    if (d.verify) {
+        const unsigned streams = (unsigned)nslots + (unsigned)d.nframes;
+        hipLaunchKernelGGL(lz4f_placed_hash_kernel, dim3((streams + kXhStreams - 1u) / kXhStreams),
+                           dim3(64), 0, s, p);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(lz4f_placed_finish_kernel, dim3((unsigned)d.nframes), dim3(64), 0, s, p);
     return hipGetLastError();
 }
 

@@ -17,6 +17,7 @@
 
 #include "../../include/ape_lz4_gpu.h"
 #include "../../include/ape_lz4f.h"
+#include "../../include/ape_lz4f_placed.h"
 #include "lz4_gpu_internal.h"
 #include "lz4_gpu_shim.h"
 
@@ -1383,6 +1384,58 @@ int APE_LZ4_lz4f_decompress_batch_dev(const char *const *d_src, const int *d_src
     d.zero = (const char *)d_scratch;
     lz4f_decode_layout(nframes, maxBlocks, &d);
     return finish_launch(launch_lz4f_decode(d, (hipStream_t)stream), "lz4f_decompress");
+}
+
+// ---- frames with short blocks (include/ape_lz4f_placed.h, lz4_decode.hip, lz4_lz4f.hip) ----
+int APE_LZ4_decompress_safe_size_batch_dev(const char *const *d_src, const int *d_srcSize,
+                                           const int *d_dstCap, const int *d_dictSize,
+                                           int *d_result, int n, void *stream) {
+    if (int rc = check_arrays("decompress_safe_size_batch_dev", n,
+                              {d_src, d_srcSize, d_dstCap, d_result}))
+        return rc;
+    if (int rc = check_device()) return rc;
+    BlockArgs a{};
+    a.src = d_src;
+    a.src_size = d_srcSize;
+    a.dst_cap = d_dstCap;
+    a.dict_size = d_dictSize;
+    a.result = d_result;
+    a.nblocks = n;
+    return finish_launch(launch_decode_size(a, (hipStream_t)stream), "lz4_decode_size_kernel");
+}
+
+size_t APE_LZ4_lz4f_decompress_placed_scratch_size(int nframes, int maxBlocks) {
+    if (nframes < 0 || maxBlocks < 1) return 0;
+    return lz4f_placed_layout(nframes, maxBlocks, nullptr);
+}
+
+int APE_LZ4_lz4f_decompress_placed_batch_dev(const char *const *d_src, const int *d_srcSize,
+                                             char *const *d_dst, const int *d_dstCap,
+                                             int *d_result, int nframes, int maxBlocks, int flags,
+                                             void *d_scratch, size_t scratch_bytes, void *stream) {
+    const char *who = "lz4f_decompress_placed_batch_dev";
+    if (int rc = check_arrays(who, nframes, {d_src, d_srcSize, d_dst, d_dstCap, d_result}))
+        return rc;
+    const size_t need = APE_LZ4_lz4f_decompress_placed_scratch_size(nframes, maxBlocks);
+    if (maxBlocks < 1 || (flags & ~3) || need == (size_t)-1 ||
+        (nframes > 0 && (!d_scratch || scratch_bytes < need || !aligned16(d_scratch))))
+        return einval("%s: nframes %d, maxBlocks %d (from 1), flags %d (0..3), scratch of %zu "
+                      "bytes at %p (need %zu bytes 16-byte aligned, fewer than 2^24 blocks)", who,
+                      nframes, maxBlocks, flags, scratch_bytes, d_scratch, need);
+    if (int rc = check_device()) return rc;
+    LfPlaced p{};
+    p.d.src = d_src;
+    p.d.src_size = d_srcSize;
+    p.d.dst = d_dst;
+    p.d.dst_cap = d_dstCap;
+    p.d.result = d_result;
+    p.d.nframes = nframes;
+    p.d.max_blocks = maxBlocks;
+    p.d.verify = !(flags & 1);
+    p.d.no_linked = (flags & 2) != 0;
+    p.d.zero = (const char *)d_scratch;
+    lz4f_placed_layout(nframes, maxBlocks, &p);
+    return finish_launch(launch_lz4f_placed(p, (hipStream_t)stream), "lz4f_decompress_placed");
 }
 
 #ifdef APE_LZ4_STATS
