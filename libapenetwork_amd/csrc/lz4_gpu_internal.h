@@ -552,6 +552,10 @@ static_assert(sizeof(LfFrame) % 16 == 0, "scratch regions");
 // ... and the per-slot arrays (slot = block q of frame f at q * nframes + f): the arguments of
 // launch_decode (_a: blocks of block-independent frames) and launch_decode_chain (_b: blocks of
 // linked frames, with the output before them as dictionary), and what the other launches need.
+// One struct for both framed decodes.  `placed` is the call of
+// include/ape_lz4f_placed.h: `cap` then holds a block's measured size once the
+// place launch has run, and the last three members are what the sizer needs besides; the call
+// of include/ape_lz4f.h leaves them null.
 struct LfDecode {
     const char *const *src;   // caller's arrays, one entry per frame
     const int *src_size;
@@ -567,27 +571,19 @@ struct LfDecode {
     int *size_a, *cap_a, *res_a, *size_b, *cap_b, *res_b, *dict_size;
     int *size, *kind, *cap;   // the block's bytes in the frame; kLf...; its room in dst
     uint32_t *want, *got;     // block checksum: the frame's, and the bytes'
+    bool placed;              // (the host's choice of kernels; no kernel reads it)
+    int *cap_s, *res_s;       // the sizer's capacity (the block maximum; 0: not sized) and result
+    int *total;               // per frame: the sum of the measured sizes, once the frame is placed
 };
-size_t lz4f_decode_layout(int nframes, int max_blocks, LfDecode *out);
-// plan, stored copies, decode, chained decode (unless no_linked), hash (when verify), finish:
-// 4 to 6 launches
-hipError_t launch_lz4f_decode(const LfDecode &d, hipStream_t s);
-
-// ---- frames with short blocks (include/ape_lz4f_placed.h) ----
 // result[i] = what decompress_safe (with a.dict_size: _usingDict) would return for block i, by
 // a dry run of the decoder's parse: a.src, a.src_size, a.dst_cap, a.dict_size (nullable) and
 // a.result are used, and nothing but a.result is written (lz4_decode.hip)
 hipError_t launch_decode_size(const BlockArgs &a, hipStream_t s);
-// The placed framed decode: LfDecode's arrays, with `cap` holding a block's measured size once
-// the place launch has run, and what the sizer needs besides.
-struct LfPlaced {
-    LfDecode d;
-    int *cap_s, *res_s;       // the sizer's capacity (the block maximum; 0: not sized) and result
-    int *total;               // per frame: the sum of the measured sizes, once the frame is placed
-};
-size_t lz4f_placed_layout(int nframes, int max_blocks, LfPlaced *out);
-// plan, size, place, stored copies, decode, chained decode (unless no_linked), hash (when
-// verify), finish: 6 to 8 launches
-hipError_t launch_lz4f_placed(const LfPlaced &p, hipStream_t s);
+// fills out's scratch fields from out->zero (out nullable); (size_t)-1 from 2^24 slots on.
+// placed: the same regions, then the sizer's two arrays per slot and the totals per frame
+size_t lz4f_decode_layout(int nframes, int max_blocks, bool placed, LfDecode *out);
+// plan, [placed: size, place,] stored copies, decode, chained decode (unless no_linked), hash
+// (when verify), finish: 4 to 6 launches, 6 to 8 when placed
+hipError_t launch_lz4f_decode(const LfDecode &d, hipStream_t s);
 
 }  // namespace apelz4

@@ -365,8 +365,13 @@ lz4f_info_kernel(const char *const *src, const int *src_size, int *info, int nfr
 
 enum : int { kLfAbsent = 0, kLfIndep = 1, kLfLinked = 2, kLfStored = 3 };
 
+// Both framed decodes run the kernels below: kPlaced is the call of
+// include/ape_lz4f_placed.h (tests/lz4fplacedmodel.py defines its codes), which
+// sizes every block before it places it.
+
 // slot i of the three decode launches: nothing to do.  The one-byte block 00 with capacity 0
 // decodes to 0 (the reference's rule) and touches the scratch's first byte alone.
+template <bool kPlaced>
 __device__ __forceinline__ void lfd_absent(const LfDecode &d, uint32_t i) {
     d.src_a[i] = d.zero;
     d.src_b[i] = d.zero;
@@ -381,11 +386,63 @@ __device__ __forceinline__ void lfd_absent(const LfDecode &d, uint32_t i) {
     d.size[i] = 0;
     d.kind[i] = kLfAbsent;
     d.cap[i] = 0;
+    if constexpr (kPlaced) d.cap_s[i] = 0;
 }
 
-// one wave per frame: lane 0 judges the header and walks the blocks, filling slot q * nframes
-// + f for block q (output position q * bmax, known because every block but the last is full);
-// the wave then marks the frame's other slots absent -- all of them when the frame has a code
+// What the frame says of a block, into the absent slot i: its bytes at s + p, its size word w,
+// its checksum, and its kind with that kind's decoder input.  then(kind) is what the caller
+// adds, called in the kind's own branch, where the kind is a constant.
+template <class Then>
+__device__ __forceinline__ void lfd_fill(const LfDecode &d, uint32_t i, gcu8 *s, uint32_t p,
+                                         uint32_t w, uint32_t flg, Then then) {
+    const uint32_t sz = w & 0x7FFFFFFFu;
+    d.data[i] = (const char *)s + p;
+    d.size[i] = (int)sz;
+    if (flg & kFlgBlockSum) d.want[i] = gload4(s + p + sz);
+    if (w >> 31) {
+        d.kind[i] = kLfStored;
+        then(kLfStored);
+    } else if (flg & kFlgLinkedOff) {
+        d.kind[i] = kLfIndep;
+        d.src_a[i] = (const char *)s + p;
+        d.size_a[i] = (int)sz;
+        then(kLfIndep);
+    } else {
+        d.kind[i] = kLfLinked;
+        d.src_b[i] = (const char *)s + p;
+        d.size_b[i] = (int)sz;
+        then(kLfLinked);
+    }
+}
+
+// Slot i goes to `at` = out + pos with `room` bytes.  In two parts, so that the grid plan keeps
+// the parent's order of stores (the position, the fill, then the kind's own fields in the
+// kind's branch) and with it its instructions: where the block goes ...
+__device__ __forceinline__ void lfd_place(const LfDecode &d, uint32_t i, char *at, int room) {
+    d.out[i] = at;
+    d.cap[i] = room;
+}
+// ... and its decoder's capacity, with the output before a linked block as its dictionary
+template <class Pos>
+__device__ __forceinline__ void lfd_place_kind(const LfDecode &d, uint32_t i, int kind, char *out,
+                                               Pos pos, int room) {
+    if (kind == kLfIndep) {
+        d.cap_a[i] = room;
+    } else if (kind == kLfLinked) {
+        const uint32_t back = (uint32_t)(pos < 65536u ? pos : 65536u);
+        d.cap_b[i] = room;
+        d.dict[i] = out + pos - back;
+        d.dict_size[i] = (int)back;
+    }
+}
+
+// One wave per frame: lane 0 judges the header and walks the blocks, filling slot q * nframes
+// + f for block q; the wave then marks the frame's other slots absent -- all of them when the
+// frame has a code.  The grid call knows where block q goes, q * bmax, because every block but
+// the last is full.  The placed call does not yet: a compressed block gets its sizer arguments
+// instead, the block maximum as capacity and for a linked frame 65536 bytes of assumed history
+// (the decoded size does not depend on the offsets; the real decode applies the true test).
+template <bool kPlaced>
 __global__ void __launch_bounds__(64)
 lz4f_decode_plan_kernel(LfDecode d) {
     const uint32_t f = blockIdx.x, lane = (uint32_t)lane_id(), nf = (uint32_t)d.nframes;
@@ -395,44 +452,34 @@ lz4f_decode_plan_kernel(LfDecode d) {
         // decoders that read it are later launches
         *(uint8_t *)d.zero = 0u;
         gcu8 *s = (gcu8 *)d.src[f];
-        const int n = d.src_size[f], cap = d.dst_cap[f];
-        char *const out = d.dst[f];
+        const int n = d.src_size[f], cap = kPlaced ? 0 : d.dst_cap[f];
+        char *const out = kPlaced ? nullptr : d.dst[f];
         const LfHead h = lf_header(s, n, d.no_linked);
         uint32_t nb = 0u, bytes = 0u, bound = 0u;
         int walk = 0;
         if (!h.code)
             walk = lf_walk(s, n, h, [&](uint32_t q, uint32_t p, uint32_t w) {
                 if (q >= (uint32_t)d.max_blocks) return;
-                const uint32_t i = q * nf + f, sz = w & 0x7FFFFFFFu;
-                const uint64_t pos = (uint64_t)q * h.bmax;
-                const int room = cap > 0 && (uint64_t)cap > pos
-                                     ? (int)umin((uint32_t)((uint64_t)cap - pos), h.bmax) : 0;
-                lfd_absent(d, i);
-                d.out[i] = out + pos;
-                d.data[i] = (const char *)s + p;
-                d.size[i] = (int)sz;
-                d.cap[i] = room;
-                if (h.flg & kFlgBlockSum) d.want[i] = gload4(s + p + sz);
-                if (w >> 31) {
-                    d.kind[i] = kLfStored;
-                } else if (h.flg & kFlgLinkedOff) {
-                    d.kind[i] = kLfIndep;
-                    d.src_a[i] = (const char *)s + p;
-                    d.size_a[i] = (int)sz;
-                    d.cap_a[i] = room;
+                const uint32_t i = q * nf + f;
+                if constexpr (kPlaced) {
+                    lfd_absent<true>(d, i);
+                    lfd_fill(d, i, s, p, w, h.flg, [&](int kind) {
+                        if (kind == kLfLinked) d.dict_size[i] = 65536;
+                        if (kind != kLfStored) d.cap_s[i] = (int)h.bmax;
+                    });
                 } else {
-                    const uint32_t back = (uint32_t)(pos < 65536u ? pos : 65536u);
-                    d.kind[i] = kLfLinked;
-                    d.src_b[i] = (const char *)s + p;
-                    d.size_b[i] = (int)sz;
-                    d.cap_b[i] = room;
-                    d.dict[i] = out + pos - back;
-                    d.dict_size[i] = (int)back;
+                    const uint64_t pos = (uint64_t)q * h.bmax;
+                    const int room = cap > 0 && (uint64_t)cap > pos
+                                         ? (int)umin((uint32_t)((uint64_t)cap - pos), h.bmax) : 0;
+                    lfd_absent<false>(d, i);
+                    lfd_place(d, i, out + pos, room);
+                    lfd_fill(d, i, s, p, w, h.flg,
+                             [&](int kind) { lfd_place_kind(d, i, kind, out, pos, room); });
                 }
             }, &nb, &bytes);
         int code = lf_bound(h, walk, nb, &bound);
         if (!code && nb > (uint32_t)d.max_blocks) code = kErange;
-        if (!code && (cap < 0 || (uint32_t)cap < bound)) code = -9;
+        if (!kPlaced && !code && (cap < 0 || (uint32_t)cap < bound)) code = -9;
         LfFrame &r = d.frame[f];
         r.code = code;
         r.nb = (int)nb;
@@ -441,10 +488,12 @@ lz4f_decode_plan_kernel(LfDecode d) {
         r.content = h.cs_lo;
         r.want = (h.flg & kFlgContentSum) && !code ? gload4(s + bytes - 4u) : 0u;
         r.got = 0u;
+        if constexpr (kPlaced) d.total[f] = 0;
         filled = code ? 0u : nb;
     }
     filled = wave_first(filled);
-    for (uint32_t q = filled + lane; q < (uint32_t)d.max_blocks; q += 64u) lfd_absent(d, q * nf + f);
+    for (uint32_t q = filled + lane; q < (uint32_t)d.max_blocks; q += 64u)
+        lfd_absent<kPlaced>(d, q * nf + f);
 }
 
 // the bytes block i decodes to, or -1: a stored block's size when it fits its room
@@ -464,6 +513,7 @@ lz4f_decode_stored_kernel(LfDecode d) {
     wave_copy((gu8 *)wave_uniform(d.out[i]), (gcu8 *)wave_uniform(d.data[i]), (uint32_t)sz);
 }
 
+template <bool kPlaced>
 __global__ void __launch_bounds__(64)
 lz4f_decode_hash_kernel(LfDecode d) {
     __shared__ __attribute__((aligned(16))) uint8_t lds[kXhLds];
@@ -481,19 +531,25 @@ lz4f_decode_hash_kernel(LfDecode d) {
                 st.out = d.got + i;
             }
         } else if (r->flg & kFlgContentSum) {
-            // The decoded bytes: full blocks, then what the last one gave.  The frame is
-            // untrusted: with a declared content size the capacity may be far below blocks x
-            // maximum, and a last block 00 "decodes" to 0 in no room at all, so the length is
-            // taken in 64 bits and nothing is hashed unless it lies inside the destination
-            // (finish then reports the block that did not fit: -4 or -5).
-            const uint32_t nb = (uint32_t)r->nb;
-            const int last = nb ? lfd_block_result(d, (nb - 1u) * (uint32_t)d.nframes + f) : 0;
-            const uint64_t n = (nb ? (uint64_t)(nb - 1u) * r->bmax : 0u) + (uint64_t)(last > 0 ? last : 0);
-            const int cap = d.dst_cap[f];
-            if (last >= 0 && cap >= 0 && n <= (uint64_t)cap) {
+            if constexpr (kPlaced) {   // the content: [0, total), inside the capacity
                 st.p = (gcu8 *)d.dst[f];
-                st.n = (uint32_t)n;
+                st.n = (uint32_t)d.total[f];
                 st.out = &r->got;
+            } else {
+                // The decoded bytes: full blocks, then what the last one gave.  The frame is
+                // untrusted: with a declared content size the capacity may be far below blocks x
+                // maximum, and a last block 00 "decodes" to 0 in no room at all, so the length is
+                // taken in 64 bits and nothing is hashed unless it lies inside the destination
+                // (finish then reports the block that did not fit: -4 or -5).
+                const uint32_t nb = (uint32_t)r->nb;
+                const int last = nb ? lfd_block_result(d, (nb - 1u) * (uint32_t)d.nframes + f) : 0;
+                const uint64_t n = (nb ? (uint64_t)(nb - 1u) * r->bmax : 0u) + (uint64_t)(last > 0 ? last : 0);
+                const int cap = d.dst_cap[f];
+                if (last >= 0 && cap >= 0 && n <= (uint64_t)cap) {
+                    st.p = (gcu8 *)d.dst[f];
+                    st.n = (uint32_t)n;
+                    st.out = &r->got;
+                }
             }
         }
         return st;
@@ -536,74 +592,12 @@ lz4f_decode_finish_kernel(LfDecode d) {
     if (lane == 0u) d.result[f] = code;
 }
 
-// ---- decode, blocks of any size (include/ape_lz4f_placed.h) ----
-// tests/lz4fplacedmodel.py is the definition of the codes.  The per-slot arrays are LfDecode's;
+// ---- the placed call's own launches: place and finish (the sizer is lz4_decode.hip's) ----
 // `cap` becomes the block's measured size, which is also the room its decoder gets.
-__device__ __forceinline__ void lfp_absent(const LfPlaced &p, uint32_t i) {
-    lfd_absent(p.d, i);
-    p.cap_s[i] = 0;
-}
-
-// one wave per frame: as lz4f_decode_plan_kernel, but where a block goes is not known yet.  A
-// compressed block gets its sizer arguments: the block maximum as capacity, and for a linked
-// frame 65536 bytes of assumed history (the decoded size does not depend on the offsets; the
-// real decode applies the true test).
-__global__ void __launch_bounds__(64)
-lz4f_placed_plan_kernel(LfPlaced p) {
-    const LfDecode &d = p.d;
-    const uint32_t f = blockIdx.x, lane = (uint32_t)lane_id(), nf = (uint32_t)d.nframes;
-    uint32_t filled = 0u;
-    if (lane == 0u) {
-        *(uint8_t *)d.zero = 0u;   // (as lz4f_decode_plan_kernel)
-        gcu8 *s = (gcu8 *)d.src[f];
-        const int n = d.src_size[f];
-        const LfHead h = lf_header(s, n, d.no_linked);
-        uint32_t nb = 0u, bytes = 0u, bound = 0u;
-        int walk = 0;
-        if (!h.code)
-            walk = lf_walk(s, n, h, [&](uint32_t q, uint32_t at, uint32_t w) {
-                if (q >= (uint32_t)d.max_blocks) return;
-                const uint32_t i = q * nf + f, sz = w & 0x7FFFFFFFu;
-                lfp_absent(p, i);
-                d.data[i] = (const char *)s + at;
-                d.size[i] = (int)sz;
-                if (h.flg & kFlgBlockSum) d.want[i] = gload4(s + at + sz);
-                if (w >> 31) {
-                    d.kind[i] = kLfStored;
-                } else if (h.flg & kFlgLinkedOff) {
-                    d.kind[i] = kLfIndep;
-                    d.src_a[i] = (const char *)s + at;
-                    d.size_a[i] = (int)sz;
-                    p.cap_s[i] = (int)h.bmax;
-                } else {
-                    d.kind[i] = kLfLinked;
-                    d.src_b[i] = (const char *)s + at;
-                    d.size_b[i] = (int)sz;
-                    d.dict_size[i] = 65536;
-                    p.cap_s[i] = (int)h.bmax;
-                }
-            }, &nb, &bytes);
-        int code = lf_bound(h, walk, nb, &bound);
-        if (!code && nb > (uint32_t)d.max_blocks) code = kErange;
-        LfFrame &r = d.frame[f];
-        r.code = code;
-        r.nb = (int)nb;
-        r.bmax = h.bmax;
-        r.flg = h.flg;
-        r.content = h.cs_lo;
-        r.want = (h.flg & kFlgContentSum) && !code ? gload4(s + bytes - 4u) : 0u;
-        r.got = 0u;
-        p.total[f] = 0;
-        filled = code ? 0u : nb;
-    }
-    filled = wave_first(filled);
-    for (uint32_t q = filled + lane; q < (uint32_t)d.max_blocks; q += 64u) lfp_absent(p, q * nf + f);
-}
-
 // the bytes block i of a planned frame decodes to, or -1: a stored block's length, else what
 // the sizer found
-__device__ __forceinline__ int lfp_measured(const LfPlaced &p, uint32_t i) {
-    return p.d.kind[i] == kLfStored ? p.d.size[i] : p.res_s[i];
+__device__ __forceinline__ int lfp_measured(const LfDecode &d, uint32_t i) {
+    return d.kind[i] == kLfStored ? d.size[i] : d.res_s[i];
 }
 
 // One wave per frame: the sizes scanned into positions and the total.  What can be decided is
@@ -612,8 +606,7 @@ __device__ __forceinline__ int lfp_measured(const LfPlaced &p, uint32_t i) {
 // frame's slots become absent; the others get their place, out = dst + pos, a room of exactly
 // the measured size, and for a linked block the output before it as dictionary.
 __global__ void __launch_bounds__(64)
-lz4f_placed_place_kernel(LfPlaced p) {
-    const LfDecode &d = p.d;
+lz4f_placed_place_kernel(LfDecode d) {
     const uint32_t f = blockIdx.x, lane = (uint32_t)lane_id(), nf = (uint32_t)d.nframes;
     LfFrame &r = d.frame[f];
     if (r.code) return;   // (its slots are absent since the plan)
@@ -624,7 +617,7 @@ lz4f_placed_place_kernel(LfPlaced p) {
     bool unsized = false;
     for (uint32_t q0 = 0; q0 < nb; q0 += 64u) {
         const uint32_t q = q0 + lane;
-        const int m = q < nb ? lfp_measured(p, q * nf + f) : 0;
+        const int m = q < nb ? lfp_measured(d, q * nf + f) : 0;
         unsized |= m < 0;
         total += lane_val(wave_incl_sum(m > 0 ? (uint32_t)m : 0u), 63);
     }
@@ -633,7 +626,7 @@ lz4f_placed_place_kernel(LfPlaced p) {
     else if (cap < 0 || total > (uint64_t)cap) code = -9;
     else if ((r.flg & kFlgSize) && (uint64_t)r.content != total) code = -8;
     if (code) {
-        for (uint32_t q = lane; q < nb; q += 64u) lfp_absent(p, q * nf + f);
+        for (uint32_t q = lane; q < nb; q += 64u) lfd_absent<true>(d, q * nf + f);
         if (lane == 0u) r.code = code;
         return;
     }
@@ -641,57 +634,22 @@ lz4f_placed_place_kernel(LfPlaced p) {
     uint32_t at = 0u;   // (total <= cap < 2^31)
     for (uint32_t q0 = 0; q0 < nb; q0 += 64u) {
         const uint32_t q = q0 + lane, i = q * nf + f;
-        const uint32_t m = q < nb ? (uint32_t)lfp_measured(p, i) : 0u;
+        const uint32_t m = q < nb ? (uint32_t)lfp_measured(d, i) : 0u;
         const uint32_t incl = wave_incl_sum(m);
         if (q < nb) {
             const uint32_t pos = at + incl - m;
             const int kind = d.kind[i];
-            d.out[i] = out + pos;
-            d.cap[i] = (int)m;
-            if (kind == kLfIndep) {
-                d.cap_a[i] = (int)m;
-            } else if (kind == kLfLinked) {
-                const uint32_t back = umin(pos, 65536u);
-                d.cap_b[i] = (int)m;
-                d.dict[i] = out + pos - back;
-                d.dict_size[i] = (int)back;
-            }
+            lfd_place(d, i, out + pos, (int)m);
+            lfd_place_kind(d, i, kind, out, pos, (int)m);
         }
         at += lane_val(incl, 63);
     }
-    if (lane == 0u) p.total[f] = (int)total;
-}
-
-__global__ void __launch_bounds__(64)
-lz4f_placed_hash_kernel(LfPlaced p) {
-    __shared__ __attribute__((aligned(16))) uint8_t lds[kXhLds];
-    const LfDecode &d = p.d;
-    const uint32_t nslots = (uint32_t)d.nframes * (uint32_t)d.max_blocks;
-    xxh32_group(lds, [&](uint32_t i) {
-        const uint32_t f = i < nslots ? i % (uint32_t)d.nframes : i - nslots;
-        LfFrame *const r = d.frame + f;
-        XStream st{nullptr, 0u, nullptr};
-        if (r->code) {
-            // nothing of a frame with a code is hashed
-        } else if (i < nslots) {   // a block, as it sits in the frame
-            if ((r->flg & kFlgBlockSum) && d.kind[i] != kLfAbsent) {
-                st.p = (gcu8 *)d.data[i];
-                st.n = (uint32_t)d.size[i];
-                st.out = d.got + i;
-            }
-        } else if (r->flg & kFlgContentSum) {   // the content: [0, total), inside the capacity
-            st.p = (gcu8 *)d.dst[f];
-            st.n = (uint32_t)p.total[f];
-            st.out = &r->got;
-        }
-        return st;
-    }, blockIdx.x * (uint32_t)kXhStreams, nslots + (uint32_t)d.nframes, 0u);
+    if (lane == 0u) d.total[f] = (int)total;
 }
 
 // one wave per frame: the place launch's code, else the first of -6, -4, -7, else the total
 __global__ void __launch_bounds__(64)
-lz4f_placed_finish_kernel(LfPlaced p) {
-    const LfDecode &d = p.d;
+lz4f_placed_finish_kernel(LfDecode d) {
     const uint32_t f = blockIdx.x, lane = (uint32_t)lane_id(), nf = (uint32_t)d.nframes;
     const LfFrame r = d.frame[f];
     int code = r.code;
@@ -707,10 +665,22 @@ lz4f_placed_finish_kernel(LfPlaced p) {
         if (wave_any(bad_sum)) code = -6;
         else if (wave_any(bad_block)) code = -4;
         else if (d.verify && (r.flg & kFlgContentSum) && r.got != r.want) code = -7;
-        else code = p.total[f];
+        else code = d.total[f];
     }
     if (lane == 0u) d.result[f] = code;
 }
+
+// ---- host side ----
+// a scratch cut into regions that start 16-byte aligned: take() is the next region's offset,
+// `at` the bytes taken so far
+struct Cutter {
+    size_t at = 0;
+    size_t take(size_t bytes) {
+        const size_t was = at;
+        at += (bytes + 15) & ~(size_t)15;
+        return was;
+    }
+};
 
 }  // namespace
 
@@ -727,17 +697,11 @@ size_t lz4f_compress_layout(int nframes, int max_src, LfCompress *out) {
     const size_t bpf = max_src > 0 ? ((size_t)max_src + kMaxBlock - 1) / kMaxBlock : 1;
     const size_t nslots = (size_t)nframes * bpf;
     if (nslots >= ((size_t)1 << 24)) return (size_t)-1;
-    auto up = [](size_t x) { return (x + 15) & ~(size_t)15; };
-    size_t at = 0;
-    auto take = [&](size_t bytes) {
-        const size_t was = at;
-        at += up(bytes);
-        return was;
-    };
-    const size_t buf = take(nslots * kMaxBlock), src = take(nslots * 8), dst = take(nslots * 8);
-    const size_t size = take(nslots * 4), cap = take(nslots * 4), res = take(nslots * 4);
-    const size_t off = take(nslots * 4), hash = take(nslots * 4);
-    const size_t total = take((size_t)nframes * 4), fhash = take((size_t)nframes * 4);
+    Cutter c;
+    const size_t buf = c.take(nslots * kMaxBlock), src = c.take(nslots * 8), dst = c.take(nslots * 8);
+    const size_t size = c.take(nslots * 4), cap = c.take(nslots * 4), res = c.take(nslots * 4);
+    const size_t off = c.take(nslots * 4), hash = c.take(nslots * 4);
+    const size_t total = c.take((size_t)nframes * 4), fhash = c.take((size_t)nframes * 4);
     if (out) {
         char *b = out->buf;
         out->bpf = (int)bpf;
@@ -753,7 +717,7 @@ size_t lz4f_compress_layout(int nframes, int max_src, LfCompress *out) {
         out->f_total = (int *)(b + total);
         out->f_hash = (uint32_t *)(b + fhash);
     }
-    return at;
+    return c.at;
 }
 
 hipError_t launch_lz4f_compress(const LfCompress &c, hipStream_t s) {
@@ -793,20 +757,19 @@ hipError_t launch_lz4f_info(const char *const *src, const int *src_size, int *in
     return hipGetLastError();
 }
 
-size_t lz4f_decode_layout(int nframes, int max_blocks, LfDecode *out) {
+size_t lz4f_decode_layout(int nframes, int max_blocks, bool placed, LfDecode *out) {
     const size_t nslots = (size_t)nframes * (size_t)max_blocks;
     if (nslots >= ((size_t)1 << 24)) return (size_t)-1;
-    auto up = [](size_t x) { return (x + 15) & ~(size_t)15; };
-    size_t at = 0;
-    auto take = [&](size_t bytes) {
-        const size_t was = at;
-        at += up(bytes);
-        return was;
-    };
-    const size_t zero = take(16), frame = take((size_t)nframes * sizeof(LfFrame));
-    size_t ptrs[5], ints[12];
-    for (size_t &p : ptrs) p = take(nslots * 8);
-    for (size_t &p : ints) p = take(nslots * 4);
+    Cutter c;
+    const size_t zero = c.take(16), frame = c.take((size_t)nframes * sizeof(LfFrame));
+    size_t ptrs[5], ints[12], sizer[3] = {0, 0, 0};
+    for (size_t &p : ptrs) p = c.take(nslots * 8);
+    for (size_t &p : ints) p = c.take(nslots * 4);
+    if (placed) {   // after the grid call's regions
+        sizer[0] = c.take(nslots * 4);
+        sizer[1] = c.take(nslots * 4);
+        sizer[2] = c.take((size_t)nframes * 4);
+    }
     if (out) {
         char *b = (char *)out->zero;
         out->zero = b + zero;
@@ -820,17 +783,35 @@ size_t lz4f_decode_layout(int nframes, int max_blocks, LfDecode *out) {
                                   &out->cap_b, &out->res_b, &out->dict_size, &out->size,
                                   &out->kind, &out->cap, (int **)&out->want, (int **)&out->got};
         for (int k = 0; k < 12; k++) *arrays[k] = (int *)(b + ints[k]);
+        out->placed = placed;
+        out->cap_s = placed ? (int *)(b + sizer[0]) : nullptr;
+        out->res_s = placed ? (int *)(b + sizer[1]) : nullptr;
+        out->total = placed ? (int *)(b + sizer[2]) : nullptr;
     }
-    return at;
+    return c.at;
 }
 
 hipError_t launch_lz4f_decode(const LfDecode &d, hipStream_t s) {
     if (d.nframes <= 0) return hipSuccess;
     hipError_t e;
     const int nslots = d.nframes * d.max_blocks;
-    hipLaunchKernelGGL(lz4f_decode_plan_kernel, dim3((unsigned)d.nframes), dim3(64), 0, s, d);
+    const dim3 frames((unsigned)d.nframes), slots((unsigned)nslots), wave(64);
+    hipLaunchKernelGGL(d.placed ? lz4f_decode_plan_kernel<true> : lz4f_decode_plan_kernel<false>,
+                       frames, wave, 0, s, d);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL(lz4f_decode_stored_kernel, dim3((unsigned)nslots), dim3(64), 0, s, d);
+    if (d.placed) {
+        BlockArgs z{};   // every slot: a stored or absent one has capacity 0 and ends at once
+        z.src = d.data;
+        z.src_size = d.size;
+        z.dst_cap = d.cap_s;
+        z.dict_size = d.dict_size;
+        z.result = d.res_s;
+        z.nblocks = nslots;
+        if ((e = launch_decode_size(z, s)) != hipSuccess) return e;
+        hipLaunchKernelGGL(lz4f_placed_place_kernel, frames, wave, 0, s, d);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(lz4f_decode_stored_kernel, slots, wave, 0, s, d);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     BlockArgs a{};
     a.src = d.src_a;
@@ -854,76 +835,12 @@ hipError_t launch_lz4f_decode(const LfDecode &d, hipStream_t s) {
     }
     if (d.verify) {
         const unsigned streams = (unsigned)nslots + (unsigned)d.nframes;
-        hipLaunchKernelGGL(lz4f_decode_hash_kernel, dim3((streams + kXhStreams - 1u) / kXhStreams),
-                           dim3(64), 0, s, d);
+        hipLaunchKernelGGL(d.placed ? lz4f_decode_hash_kernel<true> : lz4f_decode_hash_kernel<false>,
+                           dim3((streams + kXhStreams - 1u) / kXhStreams), wave, 0, s, d);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(lz4f_decode_finish_kernel, dim3((unsigned)d.nframes), dim3(64), 0, s, d);
-    return hipGetLastError();
-}
-
-// lz4f_decode_layout's regions, then the sizer's two arrays per slot and the totals per frame
-size_t lz4f_placed_layout(int nframes, int max_blocks, LfPlaced *out) {
-    const size_t base = lz4f_decode_layout(nframes, max_blocks, out ? &out->d : nullptr);
-    if (base == (size_t)-1) return base;
-    auto up = [](size_t x) { return (x + 15) & ~(size_t)15; };
-    const size_t slots = up((size_t)nframes * (size_t)max_blocks * 4);
-    if (out) {
-        // (the layout has moved d.zero from the scratch base to its first region, at offset 0)
-        char *b = (char *)out->d.zero + base;
-        out->cap_s = (int *)b;
-        out->res_s = (int *)(b + slots);
-        out->total = (int *)(b + 2 * slots);
-    }
-    return base + 2 * slots + up((size_t)nframes * 4);
-}
-
-hipError_t launch_lz4f_placed(const LfPlaced &p, hipStream_t s) {
-    const LfDecode &d = p.d;
-    if (d.nframes <= 0) return hipSuccess;
-    hipError_t e;
-    const int nslots = d.nframes * d.max_blocks;
-    hipLaunchKernelGGL(lz4f_placed_plan_kernel, dim3((unsigned)d.nframes), dim3(64), 0, s, p);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    BlockArgs z{};   // every slot: a stored or absent one has capacity 0 and ends at once
-    z.src = d.data;
-    z.src_size = d.size;
-    z.dst_cap = p.cap_s;
-    z.dict_size = d.dict_size;
-    z.result = p.res_s;
-    z.nblocks = nslots;
-    if ((e = launch_decode_size(z, s)) != hipSuccess) return e;
-    hipLaunchKernelGGL(lz4f_placed_place_kernel, dim3((unsigned)d.nframes), dim3(64), 0, s, p);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL(lz4f_decode_stored_kernel, dim3((unsigned)nslots), dim3(64), 0, s, d);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    BlockArgs a{};
-    a.src = d.src_a;
-    a.dst = d.out;
-    a.src_size = d.size_a;
-    a.dst_cap = d.cap_a;
-    a.result = d.res_a;
-    a.nblocks = nslots;
-    if ((e = launch_decode(a, false, s)) != hipSuccess) return e;
-    if (!d.no_linked) {
-        BlockArgs b{};
-        b.src = d.src_b;
-        b.dst = d.out;
-        b.src_size = d.size_b;
-        b.dst_cap = d.cap_b;
-        b.dict = d.dict;
-        b.dict_size = d.dict_size;
-        b.result = d.res_b;
-        b.nblocks = nslots;
-        if ((e = launch_decode_chain(b, d.nframes, d.max_blocks, s)) != hipSuccess) return e;
-    }
-    if (d.verify) {
-        const unsigned streams = (unsigned)nslots + (unsigned)d.nframes;
-        hipLaunchKernelGGL(lz4f_placed_hash_kernel, dim3((streams + kXhStreams - 1u) / kXhStreams),
-                           dim3(64), 0, s, p);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(lz4f_placed_finish_kernel, dim3((unsigned)d.nframes), dim3(64), 0, s, p);
+    hipLaunchKernelGGL(d.placed ? lz4f_placed_finish_kernel : lz4f_decode_finish_kernel, frames,
+                       wave, 0, s, d);
     return hipGetLastError();
 }
 

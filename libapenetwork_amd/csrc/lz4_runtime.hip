@@ -661,6 +661,42 @@ bool dt_shape_ok(int nsamples, int maxSampleSize, int segmentSize) {
            (long long)nsamples * maxSampleSize <= 0x7FFFFFFFll;
 }
 
+// ---- the framed decodes (lz4_lz4f.hip): the call of include/ape_lz4f.h and, with `placed`,
+// the one of include/ape_lz4f_placed.h ----
+size_t lz4f_decode_scratch(int nframes, int maxBlocks, bool placed) {
+    if (nframes < 0 || maxBlocks < 1) return 0;
+    return lz4f_decode_layout(nframes, maxBlocks, placed, nullptr);
+}
+
+int lz4f_decode_batch(const char *who, bool placed, const char *const *d_src,
+                      const int *d_srcSize, char *const *d_dst, const int *d_dstCap,
+                      int *d_result, int nframes, int maxBlocks, int flags, void *d_scratch,
+                      size_t scratch_bytes, void *stream) {
+    if (int rc = check_arrays(who, nframes, {d_src, d_srcSize, d_dst, d_dstCap, d_result}))
+        return rc;
+    const size_t need = lz4f_decode_scratch(nframes, maxBlocks, placed);
+    if (maxBlocks < 1 || (flags & ~3) || need == (size_t)-1 ||
+        (nframes > 0 && (!d_scratch || scratch_bytes < need || !aligned16(d_scratch))))
+        return einval("%s: nframes %d, maxBlocks %d (from 1), flags %d (0..3), scratch of %zu "
+                      "bytes at %p (need %zu bytes 16-byte aligned, fewer than 2^24 blocks)", who,
+                      nframes, maxBlocks, flags, scratch_bytes, d_scratch, need);
+    if (int rc = check_device()) return rc;
+    LfDecode d{};
+    d.src = d_src;
+    d.src_size = d_srcSize;
+    d.dst = d_dst;
+    d.dst_cap = d_dstCap;
+    d.result = d_result;
+    d.nframes = nframes;
+    d.max_blocks = maxBlocks;
+    d.verify = !(flags & 1);
+    d.no_linked = (flags & 2) != 0;
+    d.zero = (const char *)d_scratch;
+    lz4f_decode_layout(nframes, maxBlocks, placed, &d);
+    return finish_launch(launch_lz4f_decode(d, (hipStream_t)stream),
+                         placed ? "lz4f_decompress_placed" : "lz4f_decompress");
+}
+
 }  // namespace
 
 extern "C" {
@@ -1354,36 +1390,15 @@ int APE_LZ4_lz4f_info_batch_dev(const char *const *d_src, const int *d_srcSize, 
 }
 
 size_t APE_LZ4_lz4f_decompress_scratch_size(int nframes, int maxBlocks) {
-    if (nframes < 0 || maxBlocks < 1) return 0;
-    return lz4f_decode_layout(nframes, maxBlocks, nullptr);
+    return lz4f_decode_scratch(nframes, maxBlocks, false);
 }
 
 int APE_LZ4_lz4f_decompress_batch_dev(const char *const *d_src, const int *d_srcSize,
                                       char *const *d_dst, const int *d_dstCap, int *d_result,
                                       int nframes, int maxBlocks, int flags, void *d_scratch,
                                       size_t scratch_bytes, void *stream) {
-    const char *who = "lz4f_decompress_batch_dev";
-    if (int rc = check_arrays(who, nframes, {d_src, d_srcSize, d_dst, d_dstCap, d_result}))
-        return rc;
-    const size_t need = APE_LZ4_lz4f_decompress_scratch_size(nframes, maxBlocks);
-    if (maxBlocks < 1 || (flags & ~3) || need == (size_t)-1 || (nframes > 0 && (!d_scratch || scratch_bytes < need || !aligned16(d_scratch))))
-        return einval("%s: nframes %d, maxBlocks %d (from 1), flags %d (0..3), scratch of %zu "
-                      "bytes at %p (need %zu bytes 16-byte aligned, fewer than 2^24 blocks)", who,
-                      nframes, maxBlocks, flags, scratch_bytes, d_scratch, need);
-    if (int rc = check_device()) return rc;
-    LfDecode d{};
-    d.src = d_src;
-    d.src_size = d_srcSize;
-    d.dst = d_dst;
-    d.dst_cap = d_dstCap;
-    d.result = d_result;
-    d.nframes = nframes;
-    d.max_blocks = maxBlocks;
-    d.verify = !(flags & 1);
-    d.no_linked = (flags & 2) != 0;
-    d.zero = (const char *)d_scratch;
-    lz4f_decode_layout(nframes, maxBlocks, &d);
-    return finish_launch(launch_lz4f_decode(d, (hipStream_t)stream), "lz4f_decompress");
+    return lz4f_decode_batch("lz4f_decompress_batch_dev", false, d_src, d_srcSize, d_dst, d_dstCap,
+                             d_result, nframes, maxBlocks, flags, d_scratch, scratch_bytes, stream);
 }
 
 // ---- frames with short blocks (include/ape_lz4f_placed.h, lz4_decode.hip, lz4_lz4f.hip) ----
@@ -1405,37 +1420,16 @@ int APE_LZ4_decompress_safe_size_batch_dev(const char *const *d_src, const int *
 }
 
 size_t APE_LZ4_lz4f_decompress_placed_scratch_size(int nframes, int maxBlocks) {
-    if (nframes < 0 || maxBlocks < 1) return 0;
-    return lz4f_placed_layout(nframes, maxBlocks, nullptr);
+    return lz4f_decode_scratch(nframes, maxBlocks, true);
 }
 
 int APE_LZ4_lz4f_decompress_placed_batch_dev(const char *const *d_src, const int *d_srcSize,
                                              char *const *d_dst, const int *d_dstCap,
                                              int *d_result, int nframes, int maxBlocks, int flags,
                                              void *d_scratch, size_t scratch_bytes, void *stream) {
-    const char *who = "lz4f_decompress_placed_batch_dev";
-    if (int rc = check_arrays(who, nframes, {d_src, d_srcSize, d_dst, d_dstCap, d_result}))
-        return rc;
-    const size_t need = APE_LZ4_lz4f_decompress_placed_scratch_size(nframes, maxBlocks);
-    if (maxBlocks < 1 || (flags & ~3) || need == (size_t)-1 ||
-        (nframes > 0 && (!d_scratch || scratch_bytes < need || !aligned16(d_scratch))))
-        return einval("%s: nframes %d, maxBlocks %d (from 1), flags %d (0..3), scratch of %zu "
-                      "bytes at %p (need %zu bytes 16-byte aligned, fewer than 2^24 blocks)", who,
-                      nframes, maxBlocks, flags, scratch_bytes, d_scratch, need);
-    if (int rc = check_device()) return rc;
-    LfPlaced p{};
-    p.d.src = d_src;
-    p.d.src_size = d_srcSize;
-    p.d.dst = d_dst;
-    p.d.dst_cap = d_dstCap;
-    p.d.result = d_result;
-    p.d.nframes = nframes;
-    p.d.max_blocks = maxBlocks;
-    p.d.verify = !(flags & 1);
-    p.d.no_linked = (flags & 2) != 0;
-    p.d.zero = (const char *)d_scratch;
-    lz4f_placed_layout(nframes, maxBlocks, &p);
-    return finish_launch(launch_lz4f_placed(p, (hipStream_t)stream), "lz4f_decompress_placed");
+    return lz4f_decode_batch("lz4f_decompress_placed_batch_dev", true, d_src, d_srcSize, d_dst,
+                             d_dstCap, d_result, nframes, maxBlocks, flags, d_scratch,
+                             scratch_bytes, stream);
 }
 
 #ifdef APE_LZ4_STATS

@@ -9,6 +9,8 @@ import re
 
 import pytest
 
+import cheader
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OK, ENODEV, EINVAL = 0, -1, -2
 A = 4096        # a pointer that is never dereferenced: each call ends at a check
@@ -48,17 +50,7 @@ def _valid(product, name, count=1):
 
 
 def _prototypes():
-    """name -> (return type, number of parameters) of every function the new header declares:
-    tests/test_launcher_args.py's expression, on ape_lz4_cdicts.h."""
-    src = open(os.path.join(ROOT, "include", "ape_lz4_cdicts.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    src = re.sub(r"#define[^\n]*(\\\n[^\n]*)*", "", src)
-    protos = {}
-    for m in re.finditer(r"([A-Za-z_][\w \t\n\*]*?)\b(APE_LZ4_\w+)\s*\(([^()]*)\)\s*;", src):
-        params = m.group(3).strip()
-        protos[m.group(2)] = (" ".join(m.group(1).split()),
-                              0 if params in ("", "void") else params.count(",") + 1)
-    return protos
+    return cheader.prototypes(os.path.join(ROOT, "include", "ape_lz4_cdicts.h"))
 
 
 def test_the_header_declares_the_five_and_the_binding_agrees(product):

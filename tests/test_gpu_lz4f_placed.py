@@ -237,3 +237,56 @@ def test_an_empty_batch_launches_nothing(product, cuda):
     L = product.lib()
     assert L.APE_LZ4_lz4f_decompress_placed_batch_dev(None, None, None, None, None, 0, 4, 0, None,
                                                       0, None) == 0
+
+
+# ---- more than 64 blocks (tests/lz4fmany.py): the kernels step over a frame's blocks 64 at a
+# time; tests/test_lz4f_placed_model.py has the CPU half ----
+def test_frames_of_64_65_and_130_short_blocks(product, cuda):
+    """Beside a one-block frame, whose other 129 slots are absent: the content at the exact
+    capacity, -9 and an untouched destination one byte short, -5 from the existing call."""
+    import lz4fmany as X
+    made = X.short_frames() + [X.one_block()]
+    frames, contents = [m[0] for m in made], [m[1] for m in made]
+    caps = [len(c) for c in contents]
+    assert caps[5] == 1690
+    rs, outs, _ = _decode(cuda, product, frames, caps, max_blocks=X.SHORT_BLOCKS)
+    assert rs == caps
+    assert outs == contents
+    want = [P.decode_placed(f, c - 1, X.SHORT_BLOCKS) for f, c in zip(frames, caps)]
+    assert want == [(-9, None)] * len(frames)
+    rs, _, clean = _decode(cuda, product, frames, [c - 1 for c in caps], max_blocks=X.SHORT_BLOCKS)
+    assert rs == [-9] * len(frames) and all(clean)
+    roomy = [X.bound(f) for f in frames]
+    old = [M.decode(f, c, X.SHORT_BLOCKS)[0] for f, c in zip(frames, roomy)]
+    assert old == [-5] * 6 + [13]
+    rs, outs, _ = _decode(cuda, product, frames, roomy, max_blocks=X.SHORT_BLOCKS, placed=False)
+    assert rs == old and outs[6] == contents[6]
+
+
+def test_a_bad_block_beyond_the_first_chunk_of_64(product, cuda):
+    """Block 70 without a size: -4 and nothing written.  A flipped literal in block 100: -6."""
+    import lz4fmany as X
+    good, content = X.short_frames()[2]
+    frames = [X.unsized_block_70(), good, X.flipped_block_100(), X.one_block()[0]]
+    caps = [1 << 16, len(content), 1690, 13]
+    want = [P.decode_placed(f, c, X.SHORT_BLOCKS) for f, c in zip(frames, caps)]
+    assert [w[0] for w in want] == [-4, len(content), -6, 13]
+    rs, outs, clean = _decode(cuda, product, frames, caps, max_blocks=X.SHORT_BLOCKS)
+    assert rs == [w[0] for w in want]
+    assert clean[0] and outs[1] == content and outs[3] == want[3][1]
+
+
+def test_both_calls_on_66_and_67_blocks_with_65_full_ones(product, cuda):
+    """65 full blocks and a short last one: both calls give the content.  With a 100-byte block
+    at index 64 besides, the existing call gives -5 and the placed call the content."""
+    import lz4fmany as X
+    made, want = X.big_frames(), X.big_results()
+    frames = [m[0] for m in made]
+    caps = [X.bound(f) for f in frames]
+    assert [w[1][0] for w in want] == [4259940, 4259940, 4260040, 4260040]
+    assert [w[0][0] for w in want] == [4259940, 4259940, -5, -5]
+    rs_new, outs_new, _ = _decode(cuda, product, frames, caps, max_blocks=X.BIG_BLOCKS)
+    rs_old, outs_old, _ = _decode(cuda, product, frames, caps, max_blocks=X.BIG_BLOCKS, placed=False)
+    assert rs_new == [w[1][0] for w in want] and rs_old == [w[0][0] for w in want]
+    assert outs_new == [m[1] for m in made]
+    assert outs_old[:2] == [m[1] for m in made[:2]]

@@ -5,9 +5,10 @@ APE_LZ4_ prefix, then a colon), and the binding's ctypes signatures agree with t
 per-family files (tests/test_*_args.py) pin each family's further rules."""
 import ctypes as C
 import os
-import re
 
 import pytest
+
+import cheader
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OK, ENODEV, EINVAL, ELAUNCH = 0, -1, -2, -3
@@ -85,16 +86,7 @@ EVENTS_FIRST, MS4 = "compress_large_timed_dev", 11
 
 
 def _prototypes():
-    """name -> (return type, number of parameters) of every function the header declares."""
-    src = open(os.path.join(ROOT, "include", "ape_lz4_gpu.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    src = re.sub(r"#define[^\n]*(\\\n[^\n]*)*", "", src)
-    protos = {}
-    for m in re.finditer(r"([A-Za-z_][\w \t\n\*]*?)\b(APE_LZ4_\w+)\s*\(([^()]*)\)\s*;", src):
-        params = m.group(3).strip()
-        protos[m.group(2)] = (" ".join(m.group(1).split()),
-                              0 if params in ("", "void") else params.count(",") + 1)
-    return protos
+    return cheader.prototypes(os.path.join(ROOT, "include", "ape_lz4_gpu.h"))
 
 
 def _call(product, name, args):

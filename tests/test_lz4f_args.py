@@ -5,10 +5,10 @@ against the prototypes of the new header (tests/test_gpu_xxh32.py and tests/test
 have the rest)."""
 import ctypes as C
 import os
-import re
 
 import pytest
 
+import cheader
 import lz4fmodel as M
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -43,17 +43,7 @@ def _valid(name, count=1):
 
 
 def _prototypes():
-    """name -> (return type, number of parameters) of every function the new header declares:
-    tests/test_launcher_args.py's expression, on ape_lz4f.h."""
-    src = open(os.path.join(ROOT, "include", "ape_lz4f.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    src = re.sub(r"#define[^\n]*(\\\n[^\n]*)*", "", src)
-    protos = {}
-    for m in re.finditer(r"([A-Za-z_][\w \t\n\*]*?)\b(APE_LZ4_\w+)\s*\(([^()]*)\)\s*;", src):
-        params = m.group(3).strip()
-        protos[m.group(2)] = (" ".join(m.group(1).split()),
-                              0 if params in ("", "void") else params.count(",") + 1)
-    return protos
+    return cheader.prototypes(os.path.join(ROOT, "include", "ape_lz4f.h"))
 
 
 def test_the_header_declares_the_seven_and_the_binding_agrees(product):

@@ -5,9 +5,10 @@ signatures against the header's prototypes (tests/test_gpu_decode_size.py and
 tests/test_gpu_lz4f_placed.py have the rest)."""
 import ctypes as C
 import os
-import re
 
 import pytest
+
+import cheader
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "ape_lz4f_placed.h")
@@ -37,17 +38,7 @@ def _valid(name, count=1):
 
 
 def _prototypes():
-    """name -> (return type, number of parameters) of every function the header declares:
-    tests/test_lz4f_args.py's expression, on ape_lz4f_placed.h."""
-    src = open(HEADER).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    src = re.sub(r"#define[^\n]*(\\\n[^\n]*)*", "", src)
-    protos = {}
-    for m in re.finditer(r"([A-Za-z_][\w \t\n\*]*?)\b(APE_LZ4_\w+)\s*\(([^()]*)\)\s*;", src):
-        params = m.group(3).strip()
-        protos[m.group(2)] = (" ".join(m.group(1).split()),
-                              0 if params in ("", "void") else params.count(",") + 1)
-    return protos
+    return cheader.prototypes(HEADER)
 
 
 def test_the_header_declares_the_three_and_the_binding_agrees(product):

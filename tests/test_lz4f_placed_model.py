@@ -173,3 +173,48 @@ def test_a_block_without_a_size_and_a_block_that_reaches_too_far(linked):
     code, head, blocks, _, _ = M._stage(frame)
     assert P.sizes(frame, head, blocks) == ([32] if linked else [None])
     assert P.decode_placed(frame, 1 << 16) == (-4, None)
+
+
+# ---- frames of more than 64 blocks (tests/lz4fmany.py): the CPU half of the GPU tests ----
+def test_the_many_block_frames_are_what_the_gpu_tests_take_them_to_be():
+    import lz4fmany as X
+    frames = X.short_frames()
+    assert [P.blocks_of(f) for f, _ in frames] == [64, 64, 65, 65, 130, 130]
+    assert [bool(M.info(f)[1] & M.F_INDEP) for f, _ in frames] == [True, False] * 3
+    for frame, content in frames:
+        n = len(content)
+        assert n == 13 * P.blocks_of(frame) and M.info(frame)[1] & (M.F_BSUM | M.F_CSUM | M.F_SIZE) \
+            == M.F_BSUM | M.F_CSUM | M.F_SIZE
+        assert P.decode_placed(frame, n, X.SHORT_BLOCKS) == (n, content)
+        assert P.decode_placed(frame, n - 1, X.SHORT_BLOCKS) == (-9, None)
+        assert M.decode(frame, X.bound(frame), X.SHORT_BLOCKS) == (-5, None)
+    assert len(frames[5][1]) == 1690
+    one, content = X.one_block()
+    assert P.blocks_of(one) == 1 and P.decode_placed(one, 13, X.SHORT_BLOCKS) == (13, content)
+
+
+def test_a_bad_block_beyond_the_first_chunk_of_64():
+    import lz4fmany as X
+    frame = X.unsized_block_70()
+    code, head, blocks, _, _ = M._stage(frame)
+    assert code == 0 and len(blocks) == 130 and head.flg & M.F_INDEP
+    measured = P.sizes(frame, head, blocks)
+    assert [q for q, n in enumerate(measured) if n is None] == [70]
+    assert P.decode_placed(frame, 1 << 16, X.SHORT_BLOCKS) == (-4, None)
+    frame = X.flipped_block_100()
+    code, head, blocks, _, _ = M._stage(frame)
+    assert code == 0 and len(blocks) == 130 and not head.flg & M.F_INDEP
+    assert [q for q, b in enumerate(blocks) if M.xxh32(frame[b.at:b.at + b.size]) != b.want] == [100]
+    assert P.decode_placed(frame, 1690, X.SHORT_BLOCKS) == (-6, None)
+    assert P.decode_placed(frame, 1690, X.SHORT_BLOCKS, M.NO_VERIFY)[0] == 1690
+
+
+def test_full_blocks_beyond_the_first_chunk_of_64():
+    import lz4fmany as X
+    frames = X.big_frames()
+    assert [(P.blocks_of(f), gap) for f, _, gap in frames] == [(66, False)] * 2 + [(67, True)] * 2
+    assert [bool(M.info(f)[1] & M.F_INDEP) for f, _, _ in frames] == [True, False] * 2
+    for (frame, content, gap), (old, new) in zip(frames, X.big_results()):
+        assert len(content) == (4260040 if gap else 4259940)
+        assert new == (len(content), content)
+        assert old == ((-5, None) if gap else (len(content), content))
