@@ -141,6 +141,12 @@ def lib():
             "APE_LZ4_decompress_safe_size_batch_dev": (i, [p, p, p, p, p, i, p]),
             "APE_LZ4_lz4f_decompress_placed_scratch_size": (sz, [i, i]),
             "APE_LZ4_lz4f_decompress_placed_batch_dev": (i, [p, p, p, p, p, i, i, i, p, sz, p]),
+            "APE_LZ4_lz4f_info_dict_batch_dev": (i, [p, p, p, i, p]),
+            "APE_LZ4_lz4f_compress_usingCDicts_bound": (sz, [i, i]),
+            "APE_LZ4_lz4f_compress_usingCDicts_scratch_size": (sz, [i, i, i]),
+            "APE_LZ4_lz4f_compress_usingCDicts_batch_dev": (i, [p, p, p, p, p, i, p, p, i, i, i, i, p, sz, p]),
+            "APE_LZ4_lz4f_decompress_usingDicts_scratch_size": (sz, [i, i, i]),
+            "APE_LZ4_lz4f_decompress_usingDicts_batch_dev": (i, [p, p, p, p, p, i, i, p, p, p, i, i, p, sz, p]),
             "APE_LZ4_rxbuf_new": (p, [sz]),
             "APE_LZ4_rxbuf_prepare": (i, [p, sz]),
             "APE_LZ4_rxbuf_append": (i, [p, p, sz]),
@@ -1222,6 +1228,87 @@ def lz4f_decompress_placed_batch(src_ptrs, src_sizes, dst_ptrs, caps, results, m
     bytes, 16-byte aligned.  Allocates nothing."""
     _lz4f_batch("APE_LZ4_lz4f_decompress_placed_batch_dev", "lz4f_decompress_placed_batch",
                 src_ptrs, src_sizes, dst_ptrs, caps, results, max_blocks, flags, scratch, stream)
+
+
+# ---- frames with a dictionary (include/ape_lz4f_dict.h, DESIGN.md 3.26) ----
+# (Public without a line in __all__, as the calls above; tests/test_lz4f_dict_args.py checks
+# these six.)
+LZ4F_ANY_BLOCK_SIZE = 4            # decompress flag of lz4f_decompress_dicts_batch: short blocks
+LZ4F_NO_DICTIONARY = -10           # a frame names an ID the table has no usable entry for
+
+
+def lz4f_info_dict_batch(src_ptrs, src_sizes, info, stream=None):
+    """APE_LZ4_lz4f_info_dict_batch_dev: info (int32 CUDA tensor of 10 N) gets, per frame, the
+    eight ints of lz4f_info_batch -- a dictionary ID is no reason for -3 -- then whether the
+    frame carries the ID field and the ID (its 32 bits as an int32), or 0."""
+    what = "lz4f_info_dict_batch"
+    n = _count(what, "src_sizes", src_sizes)
+    _ptr_args(what, n, src_ptrs=src_ptrs, src_sizes=src_sizes)
+    _ptr_args(what, 10 * n, info=info)
+    _call("APE_LZ4_lz4f_info_dict_batch_dev", _ptr(src_ptrs), _ptr(src_sizes), _ptr(info), n,
+          _stream(stream))
+
+
+def lz4f_compress_cdicts_bound(src_size, flags=0):
+    """APE_LZ4_lz4f_compress_usingCDicts_bound: the most bytes a one-block dictionary frame of
+    src_size (0..65536) input bytes takes with these flags (0 for arguments out of range)."""
+    return lib().APE_LZ4_lz4f_compress_usingCDicts_bound(src_size, flags)
+
+
+def lz4f_compress_cdicts_scratch_size(nframes, max_src_size, mode):
+    """APE_LZ4_lz4f_compress_usingCDicts_scratch_size: scratch bytes of one
+    lz4f_compress_cdicts_batch call in this mode."""
+    return lib().APE_LZ4_lz4f_compress_usingCDicts_scratch_size(nframes, max_src_size, mode)
+
+
+def lz4f_compress_cdicts_batch(src_ptrs, src_sizes, dst_ptrs, caps, results, cdict_ptrs, dict_ids,
+                               max_src_size, mode, depth, flags, scratch, stream=None):
+    """APE_LZ4_lz4f_compress_usingCDicts_batch_dev: message i (at most max_src_size bytes) -> one
+    LZ4 frame of one block compressed against the prepared dictionary cdict_ptrs[i] (int64 CUDA
+    tensor of device pointers: objects of cdict_prepare* for mode 0, of hc_cdict_prepare* for
+    this max_src_size for mode 1, the lazy parse, and 2, the cost-minimising parse; depth as in
+    compress_hc_cdicts_batch, 0 with mode 0).  dict_ids: int32 CUDA tensor (the IDs' 32 bits)
+    or None; the frame carries the ID field where its entry is not 0.  flags as
+    lz4f_compress_batch.  A bad object gives a valid frame with a stored block.  results[i] =
+    the frame's bytes, 0 when it does not fit caps[i] (nothing written), ERANGE above
+    max_src_size.  scratch: uint8 CUDA tensor of at least
+    lz4f_compress_cdicts_scratch_size(N, max_src_size, mode) bytes, 16-byte aligned."""
+    what = "lz4f_compress_cdicts_batch"
+    n = _ptr_batch(what, _FIVE, src_ptrs, src_sizes, dst_ptrs, caps, results, ("dict_ids",),
+                   cdict_ptrs=cdict_ptrs, dict_ids=dict_ids)
+    _bytes(scratch, what + " scratch")
+    _call("APE_LZ4_lz4f_compress_usingCDicts_batch_dev", _ptr(src_ptrs), _ptr(src_sizes),
+          _ptr(dst_ptrs), _ptr(caps), _ptr(results), n, _ptr(cdict_ptrs), _ptr(dict_ids),
+          max_src_size, mode, depth, flags, _ptr(scratch), scratch.numel(), _stream(stream))
+
+
+def lz4f_decompress_dicts_scratch_size(nframes, max_blocks, flags=0):
+    """APE_LZ4_lz4f_decompress_usingDicts_scratch_size: scratch bytes of one
+    lz4f_decompress_dicts_batch call with these flags."""
+    return lib().APE_LZ4_lz4f_decompress_usingDicts_scratch_size(nframes, max_blocks, flags)
+
+
+def lz4f_decompress_dicts_batch(src_ptrs, src_sizes, dst_ptrs, caps, results, max_blocks,
+                                table_ids, table_dict_ptrs, table_dict_sizes, flags, scratch,
+                                stream=None):
+    """APE_LZ4_lz4f_decompress_usingDicts_batch_dev: lz4f_decompress_batch (with
+    LZ4F_ANY_BLOCK_SIZE in flags: the short-block decode) for frames written with a
+    dictionary.  The table -- table_ids (int32 CUDA tensor, the IDs' 32 bits), table_dict_ptrs
+    (int64) and table_dict_sizes (int32), T >= 0 entries each -- maps a dictionary ID to a
+    dictionary; a frame's key is its ID, or 0 without the field, and the first entry with that
+    key is used.  results[i] = the decoded size or a code; LZ4F_NO_DICTIONARY (-10) for a named
+    ID without a usable entry."""
+    what = "lz4f_decompress_dicts_batch"
+    n = _ptr_batch(what, _FIVE, src_ptrs, src_sizes, dst_ptrs, caps, results)
+    t = _count(what, "table_dict_sizes", table_dict_sizes)
+    _ptr_args(what, t, table_ids=table_ids, table_dict_ptrs=table_dict_ptrs,
+              table_dict_sizes=table_dict_sizes)
+    _bytes(scratch, what + " scratch")
+    _call("APE_LZ4_lz4f_decompress_usingDicts_batch_dev", _ptr(src_ptrs), _ptr(src_sizes),
+          _ptr(dst_ptrs), _ptr(caps), _ptr(results), n, max_blocks,
+          _ptr(table_ids) if t else None, _ptr(table_dict_ptrs) if t else None,
+          _ptr(table_dict_sizes) if t else None, t, flags, _ptr(scratch), scratch.numel(),
+          _stream(stream))
 
 
 SOCKET_STATS = {"tx_h2d_ms": 0, "tx_encode_ms": 1, "tx_d2h_ms": 2, "tx_write_ms": 3,

@@ -533,20 +533,33 @@ struct LfCompress {
     uint32_t *s_off, *s_hash;      // the block's place in its frame; its checksum
     int *f_total;             // per frame: the frame's bytes, 0 when nothing is to be written
     uint32_t *f_hash;         // per frame: the content checksum
+    // the dictionary call alone (include/ape_lz4f_dict.h): one slot per frame
+    const unsigned *dict_id;  // per frame (nullable): the ID field is written where it is not 0
+    int slot;                 // bytes of a slot buffer: maxSrcSize rounded up to 16
 };
 // fills out's scratch fields from out->buf (out nullable); (size_t)-1 from 2^24 slots on
 size_t lz4f_compress_layout(int nframes, int max_src, LfCompress *out);
 // plan, encode, layout, hash (with a checksum flag), pack: 4 or 5 launches
 hipError_t launch_lz4f_compress(const LfCompress &c, hipStream_t s);
+// One block per frame against a prepared dictionary per frame: the same
+// arrays with bpf = 1 and slots of c.slot bytes.  The caller runs the plan, then the mode's
+// encoder on the s_ arrays with the frames' objects, then the rest: layout, hash, pack.
+size_t lz4f_dict_compress_layout(int nframes, int max_src, LfCompress *out);
+hipError_t launch_lz4f_dict_compress_plan(const LfCompress &c, hipStream_t s);
+hipError_t launch_lz4f_dict_compress_rest(const LfCompress &c, hipStream_t s);
 hipError_t launch_lz4f_info(const char *const *src, const int *src_size, int *info, int nframes,
                             hipStream_t s);
+// ten ints per frame: a dictionary ID is no code, [8] whether the frame has the field, [9] the ID
+hipError_t launch_lz4f_info_dict(const char *const *src, const int *src_size, int *info,
+                                 int nframes, hipStream_t s);
 // Framed decode: what the plan launch found out about a frame ...
 struct LfFrame {
     int code, nb;             // the header stage's code (0: go on); blocks
     uint32_t bmax, flg;       // block maximum; FLG
     uint32_t content;         // content size, with that bit in flg
     uint32_t want, got;       // content checksum: the frame's, and the output's
-    uint32_t pad_;            // never written or read: keeps the records 32 bytes apart
+    int dsize;                // the dictionary call alone: bytes of the frame's dictionary, 0 =
+                              // none (the other calls never write or read it)
 };
 static_assert(sizeof(LfFrame) % 16 == 0, "scratch regions");
 // ... and the per-slot arrays (slot = block q of frame f at q * nframes + f): the arguments of
@@ -574,6 +587,13 @@ struct LfDecode {
     bool placed;              // (the host's choice of kernels; no kernel reads it)
     int *cap_s, *res_s;       // the sizer's capacity (the block maximum; 0: not sized) and result
     int *total;               // per frame: the sum of the measured sizes, once the frame is placed
+    // the dictionary call alone (include/ape_lz4f_dict.h): the caller's table,
+    // key t_id[k] -> dictionary t_dict[k] of t_size[k] bytes
+    bool dicts;               // (the host's choice of kernels; no kernel reads it)
+    const unsigned *t_id;
+    const char *const *t_dict;
+    const int *t_size;
+    int ntable;
 };
 // result[i] = what decompress_safe (with a.dict_size: _usingDict) would return for block i, by
 // a dry run of the decoder's parse: a.src, a.src_size, a.dst_cap, a.dict_size (nullable) and
@@ -583,7 +603,8 @@ hipError_t launch_decode_size(const BlockArgs &a, hipStream_t s);
 // placed: the same regions, then the sizer's two arrays per slot and the totals per frame
 size_t lz4f_decode_layout(int nframes, int max_blocks, bool placed, LfDecode *out);
 // plan, [placed: size, place,] stored copies, decode, chained decode (unless no_linked), hash
-// (when verify), finish: 4 to 6 launches, 6 to 8 when placed
+// (when verify), finish: 4 to 6 launches, 6 to 8 when placed; with d.dicts the same launches, the
+// plan looking each frame's dictionary up in the table
 hipError_t launch_lz4f_decode(const LfDecode &d, hipStream_t s);
 
 }  // namespace apelz4

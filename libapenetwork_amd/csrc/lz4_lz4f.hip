@@ -4,7 +4,10 @@
 // pointer arrays in the caller's scratch, hashes, and packs or judges the frames.
 // tests/lz4fmodel.py is the definition of the frame bytes and of the decoder's codes.
 // The placed decode (include/ape_lz4f_placed.h; tests/lz4fplacedmodel.py) sizes
-// every block with launch_decode_size before it places and decodes them.
+// every block with launch_decode_size before it places and decodes them.  Frames with a dictionary
+// (include/ape_lz4f_dict.h; tests/lz4fdictmodel.py) are the same kernels with a
+// dictionary stage: an ID field in header and info, one block per frame against a prepared
+// dictionary on the compress side, a table lookup in the decode plan.
 #include "lz4_gpu_internal.h"
 
 namespace apelz4 {
@@ -174,12 +177,38 @@ lz4f_compress_plan_kernel(LfCompress c) {
     c.s_cap[i] = real ? bsz - 1 : 0;
 }
 
-// one wave per frame: where every block goes, what the frame takes, whether it fits
+// The dictionary call (include/ape_lz4f_dict.h): one lane per frame, which is one
+// slot.  The encoders read the object's header before the size, so a frame without a block
+// (size -1) costs a header read and gets 0.
+__global__ void __launch_bounds__(256)
+lz4f_dict_compress_plan_kernel(LfCompress c) {
+    const uint32_t f = blockIdx.x * 256u + threadIdx.x;
+    if (f >= (uint32_t)c.nframes) return;
+    const int n = c.src_size[f];
+    const bool real = n > 0 && n <= c.max_src;
+    c.s_src[f] = real ? c.src[f] : c.buf;
+    c.s_dst[f] = c.buf + (size_t)f * (size_t)c.slot;
+    c.s_size[f] = real ? n : -1;
+    c.s_cap[f] = real ? n - 1 : 0;
+}
+
+// the frame's dictionary ID, 0 = no field (kDict: the dictionary call)
+template <bool kDict>
+__device__ __forceinline__ uint32_t lfc_dict_id(const LfCompress &c, uint32_t f) {
+    if constexpr (kDict) return c.dict_id ? c.dict_id[f] : 0u;
+    return 0u;
+}
+
+// one wave per frame: where every block goes, what the frame takes, whether it fits.  kDict: a
+// message above its object's maxSrcSize, which only the encoder can know, is its ERANGE.
+template <bool kDict>
 __global__ void __launch_bounds__(64)
 lz4f_compress_layout_kernel(LfCompress c) {
     const uint32_t f = blockIdx.x, lane = (uint32_t)lane_id();
     const int n = c.src_size[f], cap = c.dst_cap[f];
-    if (n < 0 || n > c.max_src) {
+    bool over = n > c.max_src;
+    if constexpr (kDict) over = over || (n > 0 && c.s_res[f] == kErange);
+    if (n < 0 || over) {
         if (lane == 0) {
             c.f_total[f] = 0;
             c.result[f] = n < 0 ? 0 : kErange;
@@ -187,7 +216,7 @@ lz4f_compress_layout_kernel(LfCompress c) {
         return;
     }
     const uint32_t nb = (uint32_t)lfc_blocks(n), per = 4u + ((c.flags & 2) ? 4u : 0u);
-    uint32_t at = lfc_header_bytes(c.flags);
+    uint32_t at = lfc_header_bytes(c.flags) + (lfc_dict_id<kDict>(c, f) ? 4u : 0u);
     for (uint32_t q0 = 0; q0 < nb; q0 += 64u) {
         const uint32_t q = q0 + lane, i = f * (uint32_t)c.bpf + q;
         uint32_t bytes = 0u;
@@ -231,6 +260,7 @@ lz4f_compress_hash_kernel(LfCompress c, uint32_t first, uint32_t end) {
 }
 
 // one wave per slot: its block; the wave of a frame's slot 0 also writes header and trailer
+template <bool kDict>
 __global__ void __launch_bounds__(64)
 lz4f_compress_pack_kernel(LfCompress c) {
     const uint32_t i = blockIdx.x, f = i / (uint32_t)c.bpf, q = i % (uint32_t)c.bpf;
@@ -240,14 +270,22 @@ lz4f_compress_pack_kernel(LfCompress c) {
     const uint32_t lane = (uint32_t)lane_id();
     if (q == 0u && lane == 0u) {
         const int n = c.src_size[f];
-        uint8_t d[10];
+        const uint32_t id = lfc_dict_id<kDict>(c, f);
+        uint8_t d[kDict ? 14 : 10];
         d[0] = (uint8_t)(0x40u | kFlgLinkedOff | ((c.flags & 2) ? kFlgBlockSum : 0u) |
-                         ((c.flags & 4) ? kFlgSize : 0u) | ((c.flags & 1) ? kFlgContentSum : 0u));
+                         ((c.flags & 4) ? kFlgSize : 0u) | ((c.flags & 1) ? kFlgContentSum : 0u) |
+                         (id ? kFlgDictId : 0u));
         d[1] = 0x40u;   // block-size ID 4
         uint32_t dn = 2u;
         if (c.flags & 4) {
             for (int k = 0; k < 8; k++) d[2 + k] = k < 4 ? (uint8_t)((uint32_t)n >> (8 * k)) : 0u;
             dn = 10u;
+        }
+        if constexpr (kDict) {
+            if (id) {
+                for (int k = 0; k < 4; k++) d[dn + k] = (uint8_t)(id >> (8 * k));
+                dn += 4u;
+            }
         }
         put_le32(out, kLfMagic);
         for (uint32_t k = 0; k < dn; k++) out[4u + k] = d[k];
@@ -273,12 +311,15 @@ struct LfHead {
     int code;            // 0, -1, -3, -2
     uint32_t flg, bmax, bytes;
     uint32_t cs_lo, cs_hi;   // the content size, when flg has kFlgSize
+    uint32_t dict_id;        // the dictionary ID, when flg has kFlgDictId (kDictOk alone)
 };
 
 // The header of frame s[0, n), in the order of tests/lz4fmodel.py: each check on the bytes it
-// needs, a truncation ending the walk.
+// needs, a truncation ending the walk.  kDictOk: the calls of include/ape_lz4f_dict.h, for which
+// a dictionary ID is a field and no reason for -3.
+template <bool kDictOk = false>
 __device__ __forceinline__ LfHead lf_header(gcu8 *s, int n, bool no_linked) {
-    LfHead h{0, 0u, 0u, 0u, 0u, 0u};
+    LfHead h{0, 0u, 0u, 0u, 0u, 0u, 0u};
     if (n < 4) return h.code = -2, h;
     const uint32_t magic = gload4(s);
     if ((magic & 0xFFFFFFF0u) == kLfSkipMagic || magic == kLfLegacyMagic) return h.code = -3, h;
@@ -300,7 +341,14 @@ __device__ __forceinline__ LfHead lf_header(gcu8 *s, int n, bool no_linked) {
         h.cs_lo = (uint32_t)d[2] | (uint32_t)d[3] << 8 | (uint32_t)d[4] << 16 | (uint32_t)d[5] << 24;
         h.cs_hi = (uint32_t)d[6] | (uint32_t)d[7] << 8 | (uint32_t)d[8] << 16 | (uint32_t)d[9] << 24;
     }
-    if ((flg & kFlgDictId) || (no_linked && !(flg & kFlgLinkedOff)) ||
+    if constexpr (kDictOk) {
+        if (flg & kFlgDictId) {
+            const uint32_t k = dn - 4u;
+            h.dict_id = (uint32_t)d[k] | (uint32_t)d[k + 1u] << 8 | (uint32_t)d[k + 2u] << 16 |
+                        (uint32_t)d[k + 3u] << 24;
+        }
+    }
+    if ((!kDictOk && (flg & kFlgDictId)) || (no_linked && !(flg & kFlgLinkedOff)) ||
         ((flg & kFlgSize) && (h.cs_hi || h.cs_lo >= 0x80000000u)))
         return h.code = -3, h;
     return h;
@@ -341,17 +389,18 @@ __device__ __forceinline__ int lf_bound(const LfHead &h, int walk, uint32_t nb, 
     return 0;
 }
 
+template <bool kDict>
 __global__ void __launch_bounds__(64)
 lz4f_info_kernel(const char *const *src, const int *src_size, int *info, int nframes) {
     const int f = (int)(blockIdx.x * 64u + threadIdx.x);
     if (f >= nframes) return;
     gcu8 *s = (gcu8 *)src[f];
     const int n = src_size[f];
-    const LfHead h = lf_header(s, n, false);
+    const LfHead h = lf_header<kDict>(s, n, false);
     uint32_t nb = 0u, bytes = 0u, bound = 0u;
     const int walk = h.code ? 0 : lf_walk(s, n, h, [](uint32_t, uint32_t, uint32_t) {}, &nb, &bytes);
     const int code = lf_bound(h, walk, nb, &bound);
-    int *o = info + 8 * (size_t)f;
+    int *o = info + (kDict ? 10 : 8) * (size_t)f;
     const bool sized = !code && (h.flg & kFlgSize);
     o[0] = code;
     o[1] = code ? 0 : (int)h.flg;
@@ -361,6 +410,11 @@ lz4f_info_kernel(const char *const *src, const int *src_size, int *info, int nfr
     o[5] = code ? 0 : (int)bound;
     o[6] = sized ? (int)h.cs_lo : -1;
     o[7] = sized ? (int)h.cs_hi : -1;
+    if constexpr (kDict) {
+        const bool field = !code && (h.flg & kFlgDictId);
+        o[8] = field ? 1 : 0;
+        o[9] = field ? (int)h.dict_id : 0;
+    }
 }
 
 enum : int { kLfAbsent = 0, kLfIndep = 1, kLfLinked = 2, kLfStored = 3 };
@@ -442,11 +496,53 @@ __device__ __forceinline__ void lfd_place_kind(const LfDecode &d, uint32_t i, in
 // the last is full.  The placed call does not yet: a compressed block gets its sizer arguments
 // instead, the block maximum as capacity and for a linked frame 65536 bytes of assumed history
 // (the decoded size does not depend on the offsets; the real decode applies the true test).
-template <bool kPlaced>
+// kDict (include/ape_lz4f_dict.h): between the header and the walk the whole wave
+// looks the frame's key up in the caller's table -- the dictionary ID, 0 without the field --
+// 64 entries per step, the first match winning.  The frame's dictionary then is the history of
+// every compressed block of an independent frame and of block 0 of a linked one, for the sizer
+// too (the true test, not the assumed 64 KiB).  A named ID without a usable entry is -10.
+template <bool kPlaced, bool kDict>
 __global__ void __launch_bounds__(64)
 lz4f_decode_plan_kernel(LfDecode d) {
     const uint32_t f = blockIdx.x, lane = (uint32_t)lane_id(), nf = (uint32_t)d.nframes;
     uint32_t filled = 0u;
+    LfHead hd{0, 0u, 0u, 0u, 0u, 0u, 0u};
+    const char *dict = nullptr;   // the frame's dictionary, wave-uniform
+    int dsize = 0;
+    bool missing = false;
+    if constexpr (kDict) {
+        uint32_t live = 0u, key = 0u, named = 0u;
+        if (lane == 0u) {
+            hd = lf_header<true>((gcu8 *)d.src[f], d.src_size[f], d.no_linked);
+            live = hd.code ? 0u : 1u;
+            key = hd.dict_id;
+            named = hd.flg & kFlgDictId;
+        }
+        live = wave_first(live);
+        key = wave_first(key);
+        named = wave_first(named);
+        if (live) {
+            int found = -1;
+            const uint32_t nt = (uint32_t)d.ntable;
+            for (uint32_t base = 0u; base < nt; base += 64u) {
+                const uint32_t k = base + lane;
+                const uint64_t hits = wave_ballot(k < nt && d.t_id[k] == key);
+                if (hits) {
+                    found = (int)(base + (uint32_t)__builtin_ctzll(hits));
+                    break;
+                }
+            }
+            if (found >= 0) {
+                const int sz = d.t_size[found];
+                const char *p = d.t_dict[found];
+                // an unusable entry: nothing is read through it
+                if (sz < 0 || (sz > 0 && !p)) missing = true;
+                else if (sz > 0) dict = p, dsize = sz;
+            } else {
+                missing = named != 0u;
+            }
+        }
+    }
     if (lane == 0u) {
         // the absent slots' block, 00: every frame's wave writes the same byte, and the
         // decoders that read it are later launches
@@ -454,7 +550,16 @@ lz4f_decode_plan_kernel(LfDecode d) {
         gcu8 *s = (gcu8 *)d.src[f];
         const int n = d.src_size[f], cap = kPlaced ? 0 : d.dst_cap[f];
         char *const out = kPlaced ? nullptr : d.dst[f];
-        const LfHead h = lf_header(s, n, d.no_linked);
+        const LfHead h = kDict ? hd : lf_header(s, n, d.no_linked);
+        // the dictionary as the history of a block that has nothing else before it
+        auto with_dict = [&](uint32_t i, uint32_t q, int kind) {
+            if constexpr (kDict) {
+                if (dsize > 0 && (kind == kLfIndep || (kind == kLfLinked && q == 0u))) {
+                    d.dict[i] = dict;
+                    d.dict_size[i] = dsize;
+                }
+            }
+        };
         uint32_t nb = 0u, bytes = 0u, bound = 0u;
         int walk = 0;
         if (!h.code)
@@ -466,6 +571,7 @@ lz4f_decode_plan_kernel(LfDecode d) {
                     lfd_fill(d, i, s, p, w, h.flg, [&](int kind) {
                         if (kind == kLfLinked) d.dict_size[i] = 65536;
                         if (kind != kLfStored) d.cap_s[i] = (int)h.bmax;
+                        with_dict(i, q, kind);
                     });
                 } else {
                     const uint64_t pos = (uint64_t)q * h.bmax;
@@ -474,11 +580,15 @@ lz4f_decode_plan_kernel(LfDecode d) {
                     lfd_absent<false>(d, i);
                     lfd_place(d, i, out + pos, room);
                     lfd_fill(d, i, s, p, w, h.flg,
-                             [&](int kind) { lfd_place_kind(d, i, kind, out, pos, room); });
+                             [&](int kind) {
+                                 lfd_place_kind(d, i, kind, out, pos, room);
+                                 with_dict(i, q, kind);
+                             });
                 }
             }, &nb, &bytes);
         int code = lf_bound(h, walk, nb, &bound);
         if (!code && nb > (uint32_t)d.max_blocks) code = kErange;
+        if (kDict && !code && missing) code = -10;
         if (!kPlaced && !code && (cap < 0 || (uint32_t)cap < bound)) code = -9;
         LfFrame &r = d.frame[f];
         r.code = code;
@@ -488,6 +598,7 @@ lz4f_decode_plan_kernel(LfDecode d) {
         r.content = h.cs_lo;
         r.want = (h.flg & kFlgContentSum) && !code ? gload4(s + bytes - 4u) : 0u;
         r.got = 0u;
+        if constexpr (kDict) r.dsize = dsize;
         if constexpr (kPlaced) d.total[f] = 0;
         filled = code ? 0u : nb;
     }
@@ -605,6 +716,11 @@ __device__ __forceinline__ int lfp_measured(const LfDecode &d, uint32_t i) {
 // total above the capacity (-9), a declared content size that is not the total (-8).  Such a
 // frame's slots become absent; the others get their place, out = dst + pos, a room of exactly
 // the measured size, and for a linked block the output before it as dictionary.
+// kDict: block 0 of a linked frame keeps the frame's dictionary, which the plan gave it.  A later
+// compressed block of such a frame that starts below 65536 would need the dictionary's tail and
+// the output before it as one history, which the block decoder does not have: the frame is -3,
+// after the sizing's -4 and before -9 and -8.
+template <bool kDict>
 __global__ void __launch_bounds__(64)
 lz4f_placed_place_kernel(LfDecode d) {
     const uint32_t f = blockIdx.x, lane = (uint32_t)lane_id(), nf = (uint32_t)d.nframes;
@@ -614,15 +730,21 @@ lz4f_placed_place_kernel(LfDecode d) {
     const int cap = d.dst_cap[f];
     // (a chunk of 64 blocks sums to at most 2^28; the total is kept in 64 bits)
     uint64_t total = 0u;
-    bool unsized = false;
+    bool unsized = false, two_part = false;
+    const bool linked_dict = kDict && r.dsize > 0 && !(r.flg & kFlgLinkedOff);
     for (uint32_t q0 = 0; q0 < nb; q0 += 64u) {
         const uint32_t q = q0 + lane;
         const int m = q < nb ? lfp_measured(d, q * nf + f) : 0;
         unsized |= m < 0;
-        total += lane_val(wave_incl_sum(m > 0 ? (uint32_t)m : 0u), 63);
+        const uint32_t mine = m > 0 ? (uint32_t)m : 0u, incl = wave_incl_sum(mine);
+        if constexpr (kDict)
+            two_part |= linked_dict && q >= 1u && q < nb && d.kind[q * nf + f] == kLfLinked &&
+                        total + (incl - mine) < 65536u;
+        total += lane_val(incl, 63);
     }
     int code = 0;
     if (wave_any(unsized)) code = -4;
+    else if (kDict && wave_any(two_part)) code = -3;
     else if (cap < 0 || total > (uint64_t)cap) code = -9;
     else if ((r.flg & kFlgSize) && (uint64_t)r.content != total) code = -8;
     if (code) {
@@ -640,7 +762,9 @@ lz4f_placed_place_kernel(LfDecode d) {
             const uint32_t pos = at + incl - m;
             const int kind = d.kind[i];
             lfd_place(d, i, out + pos, (int)m);
-            lfd_place_kind(d, i, kind, out, pos, (int)m);
+            // (block 0 of a linked frame with a dictionary keeps it)
+            if (linked_dict && q == 0u && kind == kLfLinked) d.cap_b[i] = (int)m;
+            else lfd_place_kind(d, i, kind, out, pos, (int)m);
         }
         at += lane_val(incl, 63);
     }
@@ -720,6 +844,27 @@ size_t lz4f_compress_layout(int nframes, int max_src, LfCompress *out) {
     return c.at;
 }
 
+// layout, hash (with a checksum flag), pack: what follows the encoder in both compress calls
+template <bool kDict>
+static hipError_t lz4f_compress_rest(const LfCompress &c, hipStream_t s) {
+    hipError_t e;
+    hipLaunchKernelGGL(lz4f_compress_layout_kernel<kDict>, dim3((unsigned)c.nframes), dim3(64), 0,
+                       s, c);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if (c.flags & 3) {   // block checksums are streams [0, nslots), content checksums follow
+        const uint32_t first = (c.flags & 2) ? 0u : (uint32_t)c.nslots;
+        const uint32_t end = (c.flags & 1) ? (uint32_t)c.nslots + (uint32_t)c.nframes
+                                           : (uint32_t)c.nslots;
+        hipLaunchKernelGGL(lz4f_compress_hash_kernel,
+                           dim3((end - first + kXhStreams - 1u) / kXhStreams), dim3(64), 0, s, c,
+                           first, end);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(lz4f_compress_pack_kernel<kDict>, dim3((unsigned)c.nslots), dim3(64), 0, s,
+                       c);
+    return hipGetLastError();
+}
+
 hipError_t launch_lz4f_compress(const LfCompress &c, hipStream_t s) {
     if (c.nframes <= 0) return hipSuccess;
     hipError_t e;
@@ -734,26 +879,61 @@ hipError_t launch_lz4f_compress(const LfCompress &c, hipStream_t s) {
     a.result = c.s_res;
     a.nblocks = c.nslots;
     if ((e = launch_encode(a, s)) != hipSuccess) return e;
-    hipLaunchKernelGGL(lz4f_compress_layout_kernel, dim3((unsigned)c.nframes), dim3(64), 0, s, c);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    if (c.flags & 3) {   // block checksums are streams [0, nslots), content checksums follow
-        const uint32_t first = (c.flags & 2) ? 0u : (uint32_t)c.nslots;
-        const uint32_t end = (c.flags & 1) ? (uint32_t)c.nslots + (uint32_t)c.nframes
-                                           : (uint32_t)c.nslots;
-        hipLaunchKernelGGL(lz4f_compress_hash_kernel,
-                           dim3((end - first + kXhStreams - 1u) / kXhStreams), dim3(64), 0, s, c,
-                           first, end);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(lz4f_compress_pack_kernel, dim3((unsigned)c.nslots), dim3(64), 0, s, c);
+    return lz4f_compress_rest<false>(c, s);
+}
+
+hipError_t launch_lz4f_dict_compress_plan(const LfCompress &c, hipStream_t s) {
+    if (c.nframes <= 0) return hipSuccess;
+    hipLaunchKernelGGL(lz4f_dict_compress_plan_kernel, dim3(((unsigned)c.nframes + 255u) / 256u),
+                       dim3(256), 0, s, c);
     return hipGetLastError();
+}
+
+hipError_t launch_lz4f_dict_compress_rest(const LfCompress &c, hipStream_t s) {
+    if (c.nframes <= 0) return hipSuccess;
+    return lz4f_compress_rest<true>(c, s);
+}
+
+
+size_t lz4f_dict_compress_layout(int nframes, int max_src, LfCompress *out) {
+    const size_t n = (size_t)nframes, slot = ((size_t)max_src + 15) & ~(size_t)15;
+    if (n >= ((size_t)1 << 24)) return (size_t)-1;
+    Cutter c;
+    const size_t buf = c.take(n * slot), src = c.take(n * 8), dst = c.take(n * 8);
+    size_t ints[7];   // s_size, s_cap, s_res, s_off, s_hash, f_total, f_hash
+    for (int k = 0; k < 7; k++) ints[k] = c.take(n * 4);
+    if (out) {
+        char *b = out->buf;
+        out->bpf = 1;
+        out->nslots = nframes;
+        out->slot = (int)slot;
+        out->buf = b + buf;
+        out->s_src = (const char **)(b + src);
+        out->s_dst = (char **)(b + dst);
+        out->s_size = (int *)(b + ints[0]);
+        out->s_cap = (int *)(b + ints[1]);
+        out->s_res = (int *)(b + ints[2]);
+        out->s_off = (uint32_t *)(b + ints[3]);
+        out->s_hash = (uint32_t *)(b + ints[4]);
+        out->f_total = (int *)(b + ints[5]);
+        out->f_hash = (uint32_t *)(b + ints[6]);
+    }
+    return c.at;
 }
 
 hipError_t launch_lz4f_info(const char *const *src, const int *src_size, int *info, int nframes,
                             hipStream_t s) {
     if (nframes <= 0) return hipSuccess;
-    hipLaunchKernelGGL(lz4f_info_kernel, dim3(((unsigned)nframes + 63u) / 64u), dim3(64), 0, s,
-                       src, src_size, info, nframes);
+    hipLaunchKernelGGL(lz4f_info_kernel<false>, dim3(((unsigned)nframes + 63u) / 64u), dim3(64),
+                       0, s, src, src_size, info, nframes);
+    return hipGetLastError();
+}
+
+hipError_t launch_lz4f_info_dict(const char *const *src, const int *src_size, int *info,
+                                 int nframes, hipStream_t s) {
+    if (nframes <= 0) return hipSuccess;
+    hipLaunchKernelGGL(lz4f_info_kernel<true>, dim3(((unsigned)nframes + 63u) / 64u), dim3(64), 0,
+                       s, src, src_size, info, nframes);
     return hipGetLastError();
 }
 
@@ -796,8 +976,11 @@ hipError_t launch_lz4f_decode(const LfDecode &d, hipStream_t s) {
     hipError_t e;
     const int nslots = d.nframes * d.max_blocks;
     const dim3 frames((unsigned)d.nframes), slots((unsigned)nslots), wave(64);
-    hipLaunchKernelGGL(d.placed ? lz4f_decode_plan_kernel<true> : lz4f_decode_plan_kernel<false>,
-                       frames, wave, 0, s, d);
+    void (*const plan)(LfDecode) = d.dicts ? d.placed ? lz4f_decode_plan_kernel<true, true>
+                                                      : lz4f_decode_plan_kernel<false, true>
+                                           : d.placed ? lz4f_decode_plan_kernel<true, false>
+                                                      : lz4f_decode_plan_kernel<false, false>;
+    hipLaunchKernelGGL(plan, frames, wave, 0, s, d);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     if (d.placed) {
         BlockArgs z{};   // every slot: a stored or absent one has capacity 0 and ends at once
@@ -808,7 +991,8 @@ hipError_t launch_lz4f_decode(const LfDecode &d, hipStream_t s) {
         z.result = d.res_s;
         z.nblocks = nslots;
         if ((e = launch_decode_size(z, s)) != hipSuccess) return e;
-        hipLaunchKernelGGL(lz4f_placed_place_kernel, frames, wave, 0, s, d);
+        hipLaunchKernelGGL(d.dicts ? lz4f_placed_place_kernel<true>
+                                   : lz4f_placed_place_kernel<false>, frames, wave, 0, s, d);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     hipLaunchKernelGGL(lz4f_decode_stored_kernel, slots, wave, 0, s, d);
@@ -820,6 +1004,10 @@ hipError_t launch_lz4f_decode(const LfDecode &d, hipStream_t s) {
     a.dst_cap = d.cap_a;
     a.result = d.res_a;
     a.nblocks = nslots;
+    if (d.dicts && d.ntable > 0) {   // the blocks of independent frames against their dictionaries
+        a.dict = d.dict;
+        a.dict_size = d.dict_size;
+    }
     if ((e = launch_decode(a, false, s)) != hipSuccess) return e;
     if (!d.no_linked) {
         BlockArgs b{};

@@ -18,6 +18,7 @@
 #include "../../include/ape_lz4_gpu.h"
 #include "../../include/ape_lz4f.h"
 #include "../../include/ape_lz4f_placed.h"
+#include "../../include/ape_lz4f_dict.h"
 #include "lz4_gpu_internal.h"
 #include "lz4_gpu_shim.h"
 
@@ -505,6 +506,41 @@ int hc_cdict_batch(const char *who, bool opt, const char *const *d_src, const in
                                   "lz4_hc_cdict_parse_kernel");
 }
 
+// The framed dictionary call's high-ratio passes (include/ape_lz4f_dict.h): hc_cdict_batch's
+// loop on arguments that are already checked -- three launches per pass, as many messages per
+// pass as the scratch holds slots.  d_cdicts (nullable): an object per message.
+hipError_t hc_cdict_passes(bool opt, const char *const *d_src, const int *d_srcSize,
+                           char *const *d_dst, const int *d_dstCap, int *d_result, int nblocks,
+                           const void *d_cdict, const void *const *d_cdicts, int maxSrcSize,
+                           int depth, void *d_scratch, size_t scratch_bytes, hipStream_t stream) {
+    const size_t slot = opt ? hc_cdict_opt_slot_bytes(maxSrcSize) : hc_cdict_slot_bytes(maxSrcSize);
+    const int sub = pass_blocks(scratch_bytes, slot, hc_cdict_sub(maxSrcSize), nblocks);
+    hipError_t e = hipSuccess;
+    for (int off = 0; off < nblocks && e == hipSuccess; off += sub) {
+        HcDictOptArgs o{};
+        HcDictArgs &a = o.a;
+        a.src = d_src + off;
+        a.src_size = d_srcSize + off;
+        a.dst = d_dst + off;
+        a.dst_cap = d_dstCap + off;
+        a.result = d_result + off;
+        a.nblocks = nblocks - off < sub ? nblocks - off : sub;
+        a.depth = depth ? depth : kHcDefaultDepth;
+        a.max_src = maxSrcSize;
+        a.cdict = (const uint8_t *)d_cdict;
+        a.chain_stride = (uint32_t)hc_cdict_chain_entries(maxSrcSize);
+        a.match_stride = (uint32_t)hc_cdict_match_entries(maxSrcSize);
+        a.chain = (uint16_t *)d_scratch;
+        a.match = (uint32_t *)((char *)d_scratch + (size_t)sub * a.chain_stride * sizeof(uint16_t));
+        o.cost_stride = (uint32_t)hc_cdict_cost_entries(maxSrcSize);
+        o.cost = (uint32_t *)((char *)d_scratch + (size_t)sub * hc_cdict_slot_bytes(maxSrcSize));
+        const uint8_t *const *objs = d_cdicts ? (const uint8_t *const *)d_cdicts + off : nullptr;
+        e = opt ? launch_encode_hc_cdict_opt(o, stream, objs)
+                : launch_encode_hc_cdict(a, stream, objs);
+    }
+    return e;
+}
+
 // ---- inputs of any size as one block (lz4_large.hip) ----
 constexpr int kLargeMaxSrc = 0x7E000000;   // LZ4_MAX_INPUT_SIZE (ref src/ape_lz4.h)
 
@@ -668,12 +704,22 @@ size_t lz4f_decode_scratch(int nframes, int maxBlocks, bool placed) {
     return lz4f_decode_layout(nframes, maxBlocks, placed, nullptr);
 }
 
+// The table of the dictionary call (include/ape_lz4f_dict.h); a null `table` is the other two.
+struct LfTable {
+    const unsigned *id;
+    const char *const *dict;
+    const int *size;
+    int n;
+};
+
 int lz4f_decode_batch(const char *who, bool placed, const char *const *d_src,
                       const int *d_srcSize, char *const *d_dst, const int *d_dstCap,
                       int *d_result, int nframes, int maxBlocks, int flags, void *d_scratch,
-                      size_t scratch_bytes, void *stream) {
+                      size_t scratch_bytes, void *stream, const LfTable *table = nullptr) {
     if (int rc = check_arrays(who, nframes, {d_src, d_srcSize, d_dst, d_dstCap, d_result}))
         return rc;
+    if (table && bad_arrays(table->n, {table->id, table->dict, table->size}))
+        return einval("%s: ntable %d with a null table array, or negative", who, table->n);
     const size_t need = lz4f_decode_scratch(nframes, maxBlocks, placed);
     if (maxBlocks < 1 || (flags & ~3) || need == (size_t)-1 ||
         (nframes > 0 && (!d_scratch || scratch_bytes < need || !aligned16(d_scratch))))
@@ -693,8 +739,16 @@ int lz4f_decode_batch(const char *who, bool placed, const char *const *d_src,
     d.no_linked = (flags & 2) != 0;
     d.zero = (const char *)d_scratch;
     lz4f_decode_layout(nframes, maxBlocks, placed, &d);
+    if (table) {
+        d.dicts = true;
+        d.t_id = table->id;
+        d.t_dict = table->dict;
+        d.t_size = table->size;
+        d.ntable = table->n;
+    }
     return finish_launch(launch_lz4f_decode(d, (hipStream_t)stream),
-                         placed ? "lz4f_decompress_placed" : "lz4f_decompress");
+                         table ? "lz4f_decompress_usingDicts"
+                               : placed ? "lz4f_decompress_placed" : "lz4f_decompress");
 }
 
 }  // namespace
@@ -1430,6 +1484,103 @@ int APE_LZ4_lz4f_decompress_placed_batch_dev(const char *const *d_src, const int
     return lz4f_decode_batch("lz4f_decompress_placed_batch_dev", true, d_src, d_srcSize, d_dst,
                              d_dstCap, d_result, nframes, maxBlocks, flags, d_scratch,
                              scratch_bytes, stream);
+}
+
+// ---- frames with a dictionary (include/ape_lz4f_dict.h, lz4_lz4f.hip) ----
+int APE_LZ4_lz4f_info_dict_batch_dev(const char *const *d_src, const int *d_srcSize, int *d_info,
+                                     int nframes, void *stream) {
+    if (int rc = check_arrays("lz4f_info_dict_batch_dev", nframes, {d_src, d_srcSize, d_info}))
+        return rc;
+    if (int rc = check_device()) return rc;
+    return finish_launch(launch_lz4f_info_dict(d_src, d_srcSize, d_info, nframes,
+                                               (hipStream_t)stream),
+                         "lz4f_info_kernel");
+}
+
+size_t APE_LZ4_lz4f_compress_usingCDicts_bound(int srcSize, int flags) {
+    if (srcSize < 0 || srcSize > kMaxBlock || (flags & ~7)) return 0;
+    return (size_t)((flags & 4) ? kLfHeaderMax : kLfHeaderMin) + 4 + (size_t)srcSize +
+           (srcSize ? ((flags & 2) ? 8 : 4) : 0) + ((flags & 1) ? 8 : 4);
+}
+
+size_t APE_LZ4_lz4f_compress_usingCDicts_scratch_size(int nframes, int maxSrcSize, int mode) {
+    if (nframes < 0 || maxSrcSize < 1 || maxSrcSize > kMaxBlock || mode < 0 || mode > 2) return 0;
+    const size_t frame = lz4f_dict_compress_layout(nframes, maxSrcSize, nullptr);
+    if (frame == (size_t)-1) return frame;
+    return frame + (mode ? up16(hc_cdict_scratch(nframes, maxSrcSize, mode == 2)) : 0);
+}
+
+int APE_LZ4_lz4f_compress_usingCDicts_batch_dev(const char *const *d_src, const int *d_srcSize,
+                                                char *const *d_dst, const int *d_dstCap,
+                                                int *d_result, int nframes,
+                                                const void *const *d_cdict,
+                                                const unsigned *d_dictID, int maxSrcSize, int mode,
+                                                int depth, int flags, void *d_scratch,
+                                                size_t scratch_bytes, void *stream) {
+    const char *who = "lz4f_compress_usingCDicts_batch_dev";
+    if (int rc = check_arrays(who, nframes, {d_src, d_srcSize, d_dst, d_dstCap, d_result, d_cdict}))
+        return rc;
+    const size_t need = APE_LZ4_lz4f_compress_usingCDicts_scratch_size(nframes, maxSrcSize, mode);
+    if (maxSrcSize < 1 || maxSrcSize > kMaxBlock || mode < 0 || mode > 2 || depth < 0 ||
+        depth > (mode ? kHcMaxDepth : 0) || (flags & ~7) || need == (size_t)-1 ||
+        (nframes > 0 && (!d_scratch || scratch_bytes < need || !aligned16(d_scratch))))
+        return einval("%s: nframes %d, maxSrcSize %d (1..%d), mode %d (0..2), depth %d (0..%d; 0 "
+                      "with mode 0), flags %d (0..7), scratch of %zu bytes at %p (need %zu bytes "
+                      "16-byte aligned, fewer than 2^24 frames)", who, nframes, maxSrcSize,
+                      kMaxBlock, mode, depth, kHcMaxDepth, flags, scratch_bytes, d_scratch, need);
+    if (int rc = check_device()) return rc;
+    if (nframes == 0) return APE_LZ4_GPU_OK;
+    const hipStream_t s = (hipStream_t)stream;
+    LfCompress c{};
+    c.src = d_src;
+    c.src_size = d_srcSize;
+    c.dst = d_dst;
+    c.dst_cap = d_dstCap;
+    c.result = d_result;
+    c.nframes = nframes;
+    c.max_src = maxSrcSize;
+    c.flags = flags;
+    c.dict_id = d_dictID;
+    c.buf = (char *)d_scratch;
+    const size_t frame = lz4f_dict_compress_layout(nframes, maxSrcSize, &c);
+    hipError_t e = launch_lz4f_dict_compress_plan(c, s);
+    if (e == hipSuccess && mode == 0) {
+        BlockArgs a{};
+        a.src = c.s_src;
+        a.dst = c.s_dst;
+        a.src_size = c.s_size;
+        a.dst_cap = c.s_cap;
+        a.result = c.s_res;
+        a.nblocks = nframes;
+        e = launch_encode_cdicts(a, d_cdict, s);
+    } else if (e == hipSuccess) {
+        e = hc_cdict_passes(mode == 2, c.s_src, c.s_size, c.s_dst, c.s_cap, c.s_res, nframes,
+                            nullptr, d_cdict, maxSrcSize, depth, (char *)d_scratch + frame,
+                            need - frame, s);
+    }
+    if (e == hipSuccess) e = launch_lz4f_dict_compress_rest(c, s);
+    return finish_launch(e, "lz4f_compress_usingCDicts");
+}
+
+size_t APE_LZ4_lz4f_decompress_usingDicts_scratch_size(int nframes, int maxBlocks, int flags) {
+    if (flags & ~7) return 0;
+    return lz4f_decode_scratch(nframes, maxBlocks, (flags & 4) != 0);
+}
+
+int APE_LZ4_lz4f_decompress_usingDicts_batch_dev(const char *const *d_src, const int *d_srcSize,
+                                                 char *const *d_dst, const int *d_dstCap,
+                                                 int *d_result, int nframes, int maxBlocks,
+                                                 const unsigned *d_tableID,
+                                                 const char *const *d_tableDict,
+                                                 const int *d_tableDictSize, int ntable, int flags,
+                                                 void *d_scratch, size_t scratch_bytes,
+                                                 void *stream) {
+    const char *who = "lz4f_decompress_usingDicts_batch_dev";
+    if (flags & ~7) return einval("%s: flags %d (0..7)", who, flags);
+    const LfTable table{d_tableID, d_tableDict, d_tableDictSize, ntable};
+    return lz4f_decode_batch(who, (flags & 4) != 0, d_src, d_srcSize, d_dst, d_dstCap, d_result,
+                             nframes, maxBlocks, flags & 3, d_scratch, scratch_bytes, stream,
+                             &table);
 }
 
 #ifdef APE_LZ4_STATS
