@@ -142,6 +142,9 @@ def lib():
             "APE_LZ4_lz4f_decompress_placed_scratch_size": (sz, [i, i]),
             "APE_LZ4_lz4f_decompress_placed_batch_dev": (i, [p, p, p, p, p, i, i, i, p, sz, p]),
             "APE_LZ4_lz4f_info_dict_batch_dev": (i, [p, p, p, i, p]),
+            "APE_LZ4_lz4f_compress_prefs_bound": (sz, [i, i, i]),
+            "APE_LZ4_lz4f_compress_prefs_scratch_size": (sz, [i, i, i, i, i]),
+            "APE_LZ4_lz4f_compress_prefs_batch_dev": (i, [p, p, p, p, p, i, i, i, i, i, i, p, sz, p]),
             "APE_LZ4_lz4f_compress_usingCDicts_bound": (sz, [i, i]),
             "APE_LZ4_lz4f_compress_usingCDicts_scratch_size": (sz, [i, i, i]),
             "APE_LZ4_lz4f_compress_usingCDicts_batch_dev": (i, [p, p, p, p, p, i, p, p, i, i, i, i, p, sz, p]),
@@ -1323,3 +1326,37 @@ def socket_stats(reset=True):
     if lib().APE_LZ4_socket_stats(out, 1 if reset else 0) != 0:
         raise GpuError("APE_LZ4_socket_stats failed")
     return {k: round(out[i], 3) for k, i in SOCKET_STATS.items()}
+
+
+# ---- framed compress with preferences (include/ape_lz4f_prefs.h) ----
+# (Public without a line in __all__, as the calls above; tests/test_lz4f_prefs_args.py checks
+# these three.)
+def lz4f_compress_prefs_bound(src_size, block_size_id, flags=0):
+    """APE_LZ4_lz4f_compress_prefs_bound: the most bytes a frame of src_size input bytes takes at
+    this block-size ID (4..7) with these flags (0 for arguments out of range)."""
+    return lib().APE_LZ4_lz4f_compress_prefs_bound(src_size, block_size_id, flags)
+
+
+def lz4f_compress_prefs_scratch_size(nframes, max_src_size, block_size_id, mode, pass_slices=0):
+    """APE_LZ4_lz4f_compress_prefs_scratch_size: scratch bytes of one lz4f_compress_prefs_batch
+    call; pass_slices as in compress_large_hc_scratch_size, ignored for mode 0."""
+    return lib().APE_LZ4_lz4f_compress_prefs_scratch_size(nframes, max_src_size, block_size_id,
+                                                          mode, pass_slices)
+
+
+def lz4f_compress_prefs_batch(src_ptrs, src_sizes, dst_ptrs, caps, results, max_src_size,
+                              block_size_id, mode, depth, flags, scratch, stream=None):
+    """APE_LZ4_lz4f_compress_prefs_batch_dev: lz4f_compress_batch with a block-size ID (4..7:
+    independent blocks of 64 KiB, 256 KiB, 1 MiB, 4 MiB) and an encoder (mode 0 the fast one, 1
+    the high-ratio lazy parse, 2 the cost-minimising parse; depth as in compress_large_hc, 0 with
+    mode 0).  A block is what the mode's compress_large* call writes for its range, or stored.
+    results[i] = the frame's bytes, 0 when it does not fit caps[i] (nothing written), ERANGE above
+    max_src_size.  scratch: uint8 CUDA tensor of at least
+    lz4f_compress_prefs_scratch_size(N, max_src_size, block_size_id, mode, 1) bytes, 16-byte
+    aligned; more, up to pass_slices = 0, means fewer passes and the same bytes."""
+    what = "lz4f_compress_prefs_batch"
+    n = _ptr_batch(what, _FIVE, src_ptrs, src_sizes, dst_ptrs, caps, results)
+    _bytes(scratch, what + " scratch")
+    _call("APE_LZ4_lz4f_compress_prefs_batch_dev", _ptr(src_ptrs), _ptr(src_sizes), _ptr(dst_ptrs),
+          _ptr(caps), _ptr(results), n, max_src_size, block_size_id, mode, depth, flags,
+          _ptr(scratch), scratch.numel(), _stream(stream))

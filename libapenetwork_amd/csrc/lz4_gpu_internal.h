@@ -526,7 +526,8 @@ struct LfCompress {
     int *result;
     int nframes, max_src, flags;
     int bpf, nslots;          // slots per frame, slots in all
-    char *buf;                // slot buffers of 64 KiB (the scratch base before the layout)
+    int bsid, ppb;            // block-size ID 4..7; pack pieces per slot (the layouts set both)
+    char *buf;                // slot buffers of one block (the scratch base before the layout)
     const char **s_src;       // the encoder's arguments, one entry per slot ...
     char **s_dst;
     int *s_size, *s_cap, *s_res;   // ... and its results
@@ -537,10 +538,18 @@ struct LfCompress {
     const unsigned *dict_id;  // per frame (nullable): the ID field is written where it is not 0
     int slot;                 // bytes of a slot buffer: maxSrcSize rounded up to 16
 };
-// fills out's scratch fields from out->buf (out nullable); (size_t)-1 from 2^24 slots on
-size_t lz4f_compress_layout(int nframes, int max_src, LfCompress *out);
+constexpr size_t lf_block_bytes(int bsid) { return (size_t)1 << (8 + 2 * bsid); }
+// fills out's scratch fields from out->buf (out nullable) for blocks of lf_block_bytes(bsid);
+// (size_t)-1 from 2^24 slots on
+size_t lz4f_compress_layout(int nframes, int max_src, int bsid, LfCompress *out);
 // plan, encode, layout, hash (with a checksum flag), pack: 4 or 5 launches
 hipError_t launch_lz4f_compress(const LfCompress &c, hipStream_t s);
+// The call with preferences (include/ape_lz4f_prefs.h): plan, the mode's large
+// launcher (0: launch_large at acceleration 1; 1, 2: launch_large_hc, lazy or opt, with `depth`,
+// the tables at `hc` and `pass` slices per pass) over `a`, whose five arrays are c's slot arrays
+// with nblocks = c.nslots and max_src = the block size, then layout, hash, pack.
+hipError_t launch_lz4f_prefs_compress(const LfCompress &c, const LargeArgs &a, int mode, int depth,
+                                      void *hc, int pass, hipStream_t s);
 // One block per frame against a prepared dictionary per frame: the same
 // arrays with bpf = 1 and slots of c.slot bytes.  The caller runs the plan, then the mode's
 // encoder on the s_ arrays with the frames' objects, then the rest: layout, hash, pack.

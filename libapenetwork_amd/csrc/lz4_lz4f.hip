@@ -7,7 +7,10 @@
 // every block with launch_decode_size before it places and decodes them.  Frames with a dictionary
 // (include/ape_lz4f_dict.h; tests/lz4fdictmodel.py) are the same kernels with a
 // dictionary stage: an ID field in header and info, one block per frame against a prepared
-// dictionary on the compress side, a table lookup in the decode plan.
+// dictionary on the compress side, a table lookup in the decode plan.  The call with preferences
+// (include/ape_lz4f_prefs.h; tests/lz4fprefsmodel.py) is the compress side with the
+// block size as a field, the large-input launchers as its block encoders, and a pack that cuts a
+// block into pieces.
 #include "lz4_gpu_internal.h"
 
 namespace apelz4 {
@@ -158,21 +161,27 @@ __device__ __forceinline__ void put_le32(gu8 *d, uint32_t v) {
 }
 
 // ---- compress ----
-__device__ __forceinline__ int lfc_blocks(int n) { return (int)(((uint32_t)n + 65535u) >> 16); }
+// the block size is 2^blog bytes: block-size ID 4..7 = 64 KiB .. 4 MiB
+__device__ __forceinline__ uint32_t lfc_blog(const LfCompress &c) { return 8u + 2u * (uint32_t)c.bsid; }
+__device__ __forceinline__ uint32_t lfc_blocks(int n, uint32_t blog) {
+    return (uint32_t)(((uint64_t)(uint32_t)n + ((1u << blog) - 1u)) >> blog);
+}
 __device__ __forceinline__ uint32_t lfc_header_bytes(int flags) { return (flags & 4) ? 15u : 7u; }
 
 // one lane per slot (frame f, block q at f * bpf + q): the encoder's arguments; a slot
-// without a block gets size -1, which the encoder answers with 0 before it reads anything
+// without a block gets size -1, which the encoder answers with 0 before it reads anything (the
+// large-input launchers, whose "inputs" the slots are above ID 4, do the same)
 __global__ void __launch_bounds__(256)
 lz4f_compress_plan_kernel(LfCompress c) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= (uint32_t)c.nslots) return;
     const uint32_t f = i / (uint32_t)c.bpf, q = i % (uint32_t)c.bpf;
     const int n = c.src_size[f];
-    const bool real = n > 0 && n <= c.max_src && (uint64_t)q * kMaxBlock < (uint64_t)n;
-    const int bsz = real ? (int)umin((uint32_t)n - q * (uint32_t)kMaxBlock, (uint32_t)kMaxBlock) : -1;
-    c.s_src[i] = real ? c.src[f] + (size_t)q * kMaxBlock : c.buf;
-    c.s_dst[i] = c.buf + (size_t)i * kMaxBlock;
+    const uint32_t blog = lfc_blog(c);
+    const bool real = n > 0 && n <= c.max_src && ((uint64_t)q << blog) < (uint64_t)n;
+    const int bsz = real ? (int)umin((uint32_t)n - (q << blog), 1u << blog) : -1;
+    c.s_src[i] = real ? c.src[f] + ((size_t)q << blog) : c.buf;
+    c.s_dst[i] = c.buf + ((size_t)i << blog);
     c.s_size[i] = bsz;
     c.s_cap[i] = real ? bsz - 1 : 0;
 }
@@ -215,7 +224,7 @@ lz4f_compress_layout_kernel(LfCompress c) {
         }
         return;
     }
-    const uint32_t nb = (uint32_t)lfc_blocks(n), per = 4u + ((c.flags & 2) ? 4u : 0u);
+    const uint32_t nb = lfc_blocks(n, lfc_blog(c)), per = 4u + ((c.flags & 2) ? 4u : 0u);
     uint32_t at = lfc_header_bytes(c.flags) + (lfc_dict_id<kDict>(c, f) ? 4u : 0u);
     for (uint32_t q0 = 0; q0 < nb; q0 += 64u) {
         const uint32_t q = q0 + lane, i = f * (uint32_t)c.bpf + q;
@@ -259,23 +268,35 @@ lz4f_compress_hash_kernel(LfCompress c, uint32_t first, uint32_t end) {
     }, first + blockIdx.x * (uint32_t)kXhStreams, end, 0u);
 }
 
-// one wave per slot: its block; the wave of a frame's slot 0 also writes header and trailer
+// Pack.  One wave per (slot, piece): piece p of a slot is bytes [p, p + 1) x 64 KiB of the block as
+// it sits in the frame -- the encoder's output in the slot buffer, or the source when the block
+// is stored -- so a 4 MiB block is moved by 64 waves of 64 trips each, not by one wave of 4096
+// dependent trips.  A piece starts at a multiple of 64 KiB of the block, so whole 16-byte
+// vectors of one piece never meet another's and only the block's last piece has a scalar tail:
+// every byte of the frame is written exactly once, and nothing is read outside the slot's
+// result or the source block.  The wave of a block's piece 0 writes the size word and the
+// checksum; that of a frame's slot 0 also the header and the trailer.  A wave whose piece starts
+// at or beyond the block's bytes leaves once it has read the slot's result.  With one piece per
+// slot (ID 4, and the dictionary call) this is one wave per block.
+constexpr uint32_t kLfPiece = 65536u;
+
 template <bool kDict>
 __global__ void __launch_bounds__(64)
 lz4f_compress_pack_kernel(LfCompress c) {
-    const uint32_t i = blockIdx.x, f = i / (uint32_t)c.bpf, q = i % (uint32_t)c.bpf;
+    const uint32_t i = blockIdx.x / (uint32_t)c.ppb, p = blockIdx.x % (uint32_t)c.ppb;
+    const uint32_t f = i / (uint32_t)c.bpf, q = i % (uint32_t)c.bpf;
     const int total = c.f_total[f];
     if (total <= 0) return;
     gu8 *out = (gu8 *)wave_uniform(c.dst[f]);
     const uint32_t lane = (uint32_t)lane_id();
-    if (q == 0u && lane == 0u) {
+    if (q == 0u && p == 0u && lane == 0u) {
         const int n = c.src_size[f];
         const uint32_t id = lfc_dict_id<kDict>(c, f);
         uint8_t d[kDict ? 14 : 10];
         d[0] = (uint8_t)(0x40u | kFlgLinkedOff | ((c.flags & 2) ? kFlgBlockSum : 0u) |
                          ((c.flags & 4) ? kFlgSize : 0u) | ((c.flags & 1) ? kFlgContentSum : 0u) |
                          (id ? kFlgDictId : 0u));
-        d[1] = 0x40u;   // block-size ID 4
+        d[1] = (uint8_t)((uint32_t)c.bsid << 4);
         uint32_t dn = 2u;
         if (c.flags & 4) {
             for (int k = 0; k < 8; k++) d[2 + k] = k < 4 ? (uint8_t)((uint32_t)n >> (8 * k)) : 0u;
@@ -297,13 +318,15 @@ lz4f_compress_pack_kernel(LfCompress c) {
     const int bsz = c.s_size[i];
     if (bsz <= 0) return;
     const int r = c.s_res[i];
-    const uint32_t bytes = (uint32_t)(r > 0 ? r : bsz);
+    const uint32_t bytes = (uint32_t)(r > 0 ? r : bsz), from = p * kLfPiece;
+    if (from >= bytes) return;
     gu8 *at = out + c.s_off[i];
-    if (lane == 0u) {
+    if (p == 0u && lane == 0u) {
         put_le32(at, r > 0 ? bytes : bytes | 0x80000000u);
         if (c.flags & 2) put_le32(at + 4u + bytes, c.s_hash[i]);
     }
-    wave_copy(at + 4, (gcu8 *)wave_uniform(r > 0 ? (const char *)c.s_dst[i] : c.s_src[i]), bytes);
+    gcu8 *body = (gcu8 *)wave_uniform(r > 0 ? (const char *)c.s_dst[i] : c.s_src[i]);
+    wave_copy(at + 4u + from, body + from, umin(bytes - from, kLfPiece));
 }
 
 // ---- decode ----
@@ -817,12 +840,13 @@ hipError_t launch_xxh32(const char *const *src, const int *size, uint32_t seed, 
     return hipGetLastError();
 }
 
-size_t lz4f_compress_layout(int nframes, int max_src, LfCompress *out) {
-    const size_t bpf = max_src > 0 ? ((size_t)max_src + kMaxBlock - 1) / kMaxBlock : 1;
+size_t lz4f_compress_layout(int nframes, int max_src, int bsid, LfCompress *out) {
+    const size_t block = lf_block_bytes(bsid);
+    const size_t bpf = max_src > 0 ? ((size_t)max_src + block - 1) / block : 1;
     const size_t nslots = (size_t)nframes * bpf;
     if (nslots >= ((size_t)1 << 24)) return (size_t)-1;
     Cutter c;
-    const size_t buf = c.take(nslots * kMaxBlock), src = c.take(nslots * 8), dst = c.take(nslots * 8);
+    const size_t buf = c.take(nslots * block), src = c.take(nslots * 8), dst = c.take(nslots * 8);
     const size_t size = c.take(nslots * 4), cap = c.take(nslots * 4), res = c.take(nslots * 4);
     const size_t off = c.take(nslots * 4), hash = c.take(nslots * 4);
     const size_t total = c.take((size_t)nframes * 4), fhash = c.take((size_t)nframes * 4);
@@ -830,6 +854,8 @@ size_t lz4f_compress_layout(int nframes, int max_src, LfCompress *out) {
         char *b = out->buf;
         out->bpf = (int)bpf;
         out->nslots = (int)nslots;
+        out->bsid = bsid;
+        out->ppb = (int)(block / kLfPiece);
         out->buf = b + buf;
         out->s_src = (const char **)(b + src);
         out->s_dst = (char **)(b + dst);
@@ -860,8 +886,8 @@ static hipError_t lz4f_compress_rest(const LfCompress &c, hipStream_t s) {
                            first, end);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(lz4f_compress_pack_kernel<kDict>, dim3((unsigned)c.nslots), dim3(64), 0, s,
-                       c);
+    hipLaunchKernelGGL(lz4f_compress_pack_kernel<kDict>, dim3((unsigned)c.nslots * (unsigned)c.ppb),
+                       dim3(64), 0, s, c);
     return hipGetLastError();
 }
 
@@ -879,6 +905,20 @@ hipError_t launch_lz4f_compress(const LfCompress &c, hipStream_t s) {
     a.result = c.s_res;
     a.nblocks = c.nslots;
     if ((e = launch_encode(a, s)) != hipSuccess) return e;
+    return lz4f_compress_rest<false>(c, s);
+}
+
+// The call with preferences (include/ape_lz4f_prefs.h): the slots are the
+// "inputs" of the mode's large-input launcher, `a` its arguments over the slot arrays.
+hipError_t launch_lz4f_prefs_compress(const LfCompress &c, const LargeArgs &a, int mode, int depth,
+                                      void *hc, int pass, hipStream_t s) {
+    if (c.nframes <= 0) return hipSuccess;
+    hipError_t e;
+    hipLaunchKernelGGL(lz4f_compress_plan_kernel, dim3(((unsigned)c.nslots + 255u) / 256u),
+                       dim3(256), 0, s, c);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    e = mode == 0 ? launch_large(a, 1, s) : launch_large_hc(a, depth, hc, pass, s, nullptr, mode == 2);
+    if (e != hipSuccess) return e;
     return lz4f_compress_rest<false>(c, s);
 }
 
@@ -906,6 +946,8 @@ size_t lz4f_dict_compress_layout(int nframes, int max_src, LfCompress *out) {
         char *b = out->buf;
         out->bpf = 1;
         out->nslots = nframes;
+        out->bsid = 4;
+        out->ppb = 1;   // (a slot holds at most 65536 bytes)
         out->slot = (int)slot;
         out->buf = b + buf;
         out->s_src = (const char **)(b + src);

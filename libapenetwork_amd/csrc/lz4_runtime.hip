@@ -19,6 +19,7 @@
 #include "../../include/ape_lz4f.h"
 #include "../../include/ape_lz4f_placed.h"
 #include "../../include/ape_lz4f_dict.h"
+#include "../../include/ape_lz4f_prefs.h"
 #include "lz4_gpu_internal.h"
 #include "lz4_gpu_shim.h"
 
@@ -751,6 +752,33 @@ int lz4f_decode_batch(const char *who, bool placed, const char *const *d_src,
                                : placed ? "lz4f_decompress_placed" : "lz4f_decompress");
 }
 
+// ---- framed compress with preferences (include/ape_lz4f_prefs.h, lz4_lz4f.hip) ----
+bool lf_prefs_ok(int blockSizeID, int mode) {
+    return blockSizeID >= 4 && blockSizeID <= 7 && mode >= 0 && mode <= 2;
+}
+// the scratch's three parts: the frame layer's, the large call's for the block slots as inputs
+// of up to one block, and for the high-ratio modes the tables of `want` slices per pass (0: all).
+// 0 out of range, (size_t)-1 from 2^24 block slots or slices on.
+size_t lf_prefs_scratch(int nframes, int maxSrcSize, int blockSizeID, int mode, int want,
+                        size_t *frame, size_t *large) {
+    if (nframes < 0 || maxSrcSize < 0 || maxSrcSize > kLfMaxSrc || !lf_prefs_ok(blockSizeID, mode) ||
+        want < 0)
+        return 0;
+    const int B = (int)lf_block_bytes(blockSizeID);
+    const size_t f = lz4f_compress_layout(nframes, maxSrcSize, blockSizeID, nullptr);
+    if (f == (size_t)-1) return f;
+    const long long bpf = maxSrcSize > 0 ? ((long long)maxSrcSize + B - 1) / B : 1;
+    const int nslots = (int)(nframes * bpf);
+    const size_t l = large_scratch_layout(nslots, B, nullptr);
+    if (!l) return (size_t)-1;
+    if (frame) *frame = f;
+    if (large) *large = up16(l);
+    if (mode == 0) return f + up16(l);
+    const long long S = large_slice_size(), nsl = B <= kMaxBlock ? 1 : (B + S - 1) / S;
+    return f + up16(l) + (size_t)large_hc_pass(nslots * nsl, want) *
+                             (mode == 2 ? kHcOptSlotBytes : kHcSlotBytes);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1403,7 +1431,7 @@ size_t APE_LZ4_lz4f_compress_bound(int srcSize, int flags) {
 
 size_t APE_LZ4_lz4f_compress_scratch_size(int nframes, int maxSrcSize) {
     if (nframes < 0 || maxSrcSize < 0 || maxSrcSize > kLfMaxSrc) return 0;
-    return lz4f_compress_layout(nframes, maxSrcSize, nullptr);
+    return lz4f_compress_layout(nframes, maxSrcSize, 4, nullptr);
 }
 
 int APE_LZ4_lz4f_compress_batch_dev(const char *const *d_src, const int *d_srcSize,
@@ -1430,8 +1458,74 @@ int APE_LZ4_lz4f_compress_batch_dev(const char *const *d_src, const int *d_srcSi
     c.max_src = maxSrcSize;
     c.flags = flags;
     c.buf = (char *)d_scratch;
-    lz4f_compress_layout(nframes, maxSrcSize, &c);
+    lz4f_compress_layout(nframes, maxSrcSize, 4, &c);
     return finish_launch(launch_lz4f_compress(c, (hipStream_t)stream), "lz4f_compress");
+}
+
+// ---- framed compress with preferences (include/ape_lz4f_prefs.h, lz4_lz4f.hip) ----
+size_t APE_LZ4_lz4f_compress_prefs_bound(int srcSize, int blockSizeID, int flags) {
+    if (srcSize < 0 || srcSize > kLfMaxSrc || blockSizeID < 4 || blockSizeID > 7 || (flags & ~7))
+        return 0;
+    const size_t B = lf_block_bytes(blockSizeID), nb = ((size_t)srcSize + B - 1) / B;
+    return (size_t)((flags & 4) ? kLfHeaderMax : kLfHeaderMin) + (size_t)srcSize +
+           nb * ((flags & 2) ? 8 : 4) + ((flags & 1) ? 8 : 4);
+}
+
+size_t APE_LZ4_lz4f_compress_prefs_scratch_size(int nframes, int maxSrcSize, int blockSizeID,
+                                                int mode, int passSlices) {
+    return lf_prefs_scratch(nframes, maxSrcSize, blockSizeID, mode, passSlices, nullptr, nullptr);
+}
+
+int APE_LZ4_lz4f_compress_prefs_batch_dev(const char *const *d_src, const int *d_srcSize,
+                                          char *const *d_dst, const int *d_dstCap, int *d_result,
+                                          int nframes, int maxSrcSize, int blockSizeID, int mode,
+                                          int depth, int flags, void *d_scratch,
+                                          size_t scratch_bytes, void *stream) {
+    const char *who = "lz4f_compress_prefs_batch_dev";
+    if (int rc = check_arrays(who, nframes, {d_src, d_srcSize, d_dst, d_dstCap, d_result}))
+        return rc;
+    // the least scratch: one slice per pass
+    size_t frame = 0, large = 0;
+    const size_t need = lf_prefs_scratch(nframes, maxSrcSize, blockSizeID, mode, 1, &frame, &large);
+    if (maxSrcSize < 0 || maxSrcSize > kLfMaxSrc || !lf_prefs_ok(blockSizeID, mode) || depth < 0 ||
+        depth > (mode ? kHcMaxDepth : 0) || (flags & ~7) || need == (size_t)-1 ||
+        (nframes > 0 && (!d_scratch || scratch_bytes < need || !aligned16(d_scratch))))
+        return einval("%s: nframes %d, maxSrcSize %d (0..%d), blockSizeID %d (4..7), mode %d "
+                      "(0..2), depth %d (0..%d; 0 with mode 0), flags %d (0..7), scratch of %zu "
+                      "bytes at %p (need %zu bytes 16-byte aligned, fewer than 2^24 blocks and "
+                      "slices)", who, nframes, maxSrcSize, kLfMaxSrc, blockSizeID, mode, depth,
+                      kHcMaxDepth, flags, scratch_bytes, d_scratch, need);
+    if (int rc = check_device()) return rc;
+    if (nframes == 0) return APE_LZ4_GPU_OK;
+    LfCompress c{};
+    c.src = d_src;
+    c.src_size = d_srcSize;
+    c.dst = d_dst;
+    c.dst_cap = d_dstCap;
+    c.result = d_result;
+    c.nframes = nframes;
+    c.max_src = maxSrcSize;
+    c.flags = flags;
+    c.buf = (char *)d_scratch;
+    lz4f_compress_layout(nframes, maxSrcSize, blockSizeID, &c);
+    LargeArgs a{};
+    a.src = c.s_src;
+    a.src_size = c.s_size;
+    a.dst = c.s_dst;
+    a.dst_cap = c.s_cap;
+    a.result = c.s_res;
+    a.nblocks = c.nslots;
+    a.max_src = (int)lf_block_bytes(blockSizeID);
+    a.buf = (char *)d_scratch + frame;
+    large_scratch_layout(a.nblocks, a.max_src, &a);
+    // as many slices per pass as the caller's scratch holds
+    const size_t slot = mode == 2 ? kHcOptSlotBytes : kHcSlotBytes;
+    const int pass = mode ? large_hc_pass(a.nslots, (long long)((scratch_bytes - frame - large) / slot))
+                          : 0;
+    return finish_launch(launch_lz4f_prefs_compress(c, a, mode, depth ? depth : kHcDefaultDepth,
+                                                    (char *)d_scratch + frame + large, pass,
+                                                    (hipStream_t)stream),
+                         "lz4f_compress_prefs");
 }
 
 int APE_LZ4_lz4f_info_batch_dev(const char *const *d_src, const int *d_srcSize, int *d_info,
